@@ -1,6 +1,8 @@
 """Benchmark of the hot path: frames/s of `twostream.forward` on synthetic 256x256 clips.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 without torchrun: this file starts the N ranks itself)
+    python bench.py --full                               (the headline plus every check and secondary leg below)
+    python bench.py --dump-outputs DIR                   (also write the last timed step's outputs as DIR/<name>.npy)
 
 Headline workload (BASELINE.json configs[1]): Ped2-shaped dual-stream network with a 2000-slot memory (embed_dim 64,
 k 2), inference, batch 16 per GPU, inputs resident in HBM, the package's default arithmetic (S16 = split-fp16 MFMA,
@@ -8,11 +10,14 @@ fp32-equivalent, range guard on).  One "step" = one forward over one batch.  N >
 disjoint clips (the reference has no multi-GPU semantics; inference shards by whole batches and needs no collective),
 so `scaling` is "weak" and `value` is the sum over ranks.
 
-Besides the contract fields the JSON line carries
+A plain run of the default mode (infer) sets up, warms up, times the K steps, writes its outputs if --dump-outputs
+is given and prints the contract fields (metric, value, unit, ms_per_step, higher_is_better, dtype, config).  With
+--full its JSON line also carries (the --mode train / stress / train_gan / eval_e2e legs always run as described below)
   roofline        algorithmic FLOPs of the dominant kernel per launch / its average launch duration (HIP events on the
                   launch stream), against the dense fp16 (2500) / fp32 (157.3 TFLOP/s) MFMA peak of MI355X
   parity_max_rel  max |d| / max |ref| of the LAST TIMED step's outputs against vectors recorded from the reference for
                   this very workload (tests/golden/twostream_256_b16_m2000_eval.npz); > 1e-4 -> exit code 3
+  kernels         the same per-launch durations for every kernel of the step (three more forwards)
   cpu_baseline    the CPU oracle (oracle/ammc_oracle.py, "port") timed on this host on a bounded sample (rank 0, N = 1)
 and, at N = 1 (each outside the headline's timed region; --no-secondary skips them):
   fp32_exact      the same workload on the exact-fp32 MFMA kernels (`model.precision = "fp32"`)
@@ -46,6 +51,7 @@ PEAK_HBM_GBS = 8000.0
 POWER_CEILING_TFLOPS = {"32x32x16": 1675.0, "16x16x32": 1889.0}
 PARITY_TOL = 1e-4                 # BASELINE.json north_star: 1e-4 relative fp32
 PARITY_FIXTURE = os.path.join(ROOT, "tests", "golden", "twostream_256_b16_m2000_eval.npz")
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: the most written in all
 S16_DTYPE = ("f32-equivalent: (hi,lo) f16 split, 3 fp16 MFMAs per product (v_mfma_f32_32x32x16_f16 in the 4-wave k-half-major "
              "kernels, 16x16x32 in the 8-wave / fused-decoder kernels), f32 accumulate")
 
@@ -70,6 +76,12 @@ def parse():
     p.add_argument("--sync-stats", action="store_true",
                    help="--mode train with --gpus N: BatchNorm batch statistics and the EMA codebook counts all-reduced across "
                         "the ranks (parallel.sync_statistics: N ranks x B clips = one step on N*B clips; 33 collectives per step)")
+    p.add_argument("--full", action="store_true",
+                   help="--mode infer: after the headline, also the parity check, the per-kernel / roofline table, the "
+                        "secondary legs and the CPU baseline (a plain run times the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="--mode infer: write what the last timed step returned (rank 0) as DIR/<name>.npy, float32, "
+                        f"at most {DUMP_LIMIT_BYTES >> 20} MB in all (a fixed strided sample of each array beyond that)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-secondary", action="store_true", help="headline only (profiling runs)")
     p.add_argument("--cpu-sample-batch", type=int, default=16, help="clips of the CPU baseline's forwards (the workload's own batch)")
@@ -1055,6 +1067,23 @@ def parity_against_fixture(out, fixture):
     return max(errs.values()), errs
 
 
+def dump_outputs(out_dir, out):
+    """--dump-outputs: what a caller of the timed forward receives, as <out_dir>/<name>.npy in float32.  Beyond
+    DUMP_LIMIT_BYTES in all, every array is cut to the same fixed strided sample of its flattened entries."""
+    import numpy as np
+    rgb, op, (rd, od), (rq, oq) = out
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in
+              (("rgb", rgb), ("op", op), ("rgb_diff", rd), ("op_diff", od), ("rgb_q", rq), ("op_q", oq))}
+    stride = 1
+    while sum(-(-a.size // stride) * a.itemsize for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        stride += 1
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a if stride == 1 else np.ascontiguousarray(a.reshape(-1)[::stride]))
+    if stride > 1:
+        print(f"bench.py: --dump-outputs wrote every {stride}-th entry of each flattened output", file=sys.stderr)
+
+
 def time_forward(net, rgb_x, op_x, clock, warmup, steps):
     state = {}
 
@@ -1259,18 +1288,8 @@ def run_infer(args, rank, world, dev, dist):
     elapsed, out = time_forward(net, rgb_x, op_x, clock, args.warmup, args.steps)
     if rank != 0:
         return None, 0
-
-    parity, parity_detail = None, "no reference-recorded fixture for this batch / size / slots"
-    if fixture is not None:
-        parity, parity_detail = parity_against_fixture(out, fixture)
-    elif not bool(torch.isfinite(out[0]).all()):
-        raise SystemExit("non-finite output")
-    per_kernel, dom, reps = kernel_table(net, rgb_x, op_x)
-    if (args.batch, args.size, args.n_embed, args.precision) == (16, 256, 2000, "s16"):
-        # matrix-pipe busy share of every kernel of the step from the committed PMC passes of this command (north_star asks
-        # for the MFMA utilisation of the memory-addressing GEMM: the `memory_topk_s16` row)
-        for kname, row in per_kernel.items():
-            row["mfma_busy_frac"] = pmc_busy(kname, "infer")[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     frames = args.batch * args.steps * world
     value = frames / elapsed
     flops_clip = fwd_flops_per_clip(args.size, args.size, n_embed=args.n_embed)
@@ -1289,11 +1308,25 @@ def run_infer(args, rank, world, dev, dist):
         "whole_path_tflops": round(value * flops_clip / 1e12 / world, 2),
         "precision": args.precision, "s16_range_guard": bool(getattr(net, "s16_guard", True)) if args.precision == "s16" else None,
         "s16_fallbacks": getattr(net, "s16_fallbacks", 0),
-        "parity_max_rel": parity, "parity_tol": PARITY_TOL, "parity": parity_detail,
-        "roofline": roofline_of(dom, reps, args.precision, args),
-        "kernels": per_kernel,
-        **backend_info(dist, world),
     }
+    if not args.full:
+        line.update(backend_info(dist, world))
+        return line, 0
+
+    parity, parity_detail = None, "no reference-recorded fixture for this batch / size / slots"
+    if fixture is not None:
+        parity, parity_detail = parity_against_fixture(out, fixture)
+    elif not bool(torch.isfinite(out[0]).all()):
+        raise SystemExit("non-finite output")
+    per_kernel, dom, reps = kernel_table(net, rgb_x, op_x)
+    if (args.batch, args.size, args.n_embed, args.precision) == (16, 256, 2000, "s16"):
+        # matrix-pipe busy share of every kernel of the step from the committed PMC passes of this command (north_star asks
+        # for the MFMA utilisation of the memory-addressing GEMM: the `memory_topk_s16` row)
+        for kname, row in per_kernel.items():
+            row["mfma_busy_frac"] = pmc_busy(kname, "infer")[0]
+    line.update({"parity_max_rel": parity, "parity_tol": PARITY_TOL, "parity": parity_detail,
+                 "roofline": roofline_of(dom, reps, args.precision, args), "kernels": per_kernel})
+    line.update(backend_info(dist, world))
     rc = 0 if (parity is None or parity <= PARITY_TOL) else 3
 
     if world == 1 and not args.no_secondary and (args.batch, args.size) == (16, 256):
@@ -1346,6 +1379,8 @@ def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--cpu-child":
         sys.exit(_cpu_child(sys.argv[2]))
     args = parse()
+    if args.dump_outputs and args.mode != "infer":
+        raise SystemExit("--dump-outputs writes the outputs of --mode infer only")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
     t_start = time.perf_counter()

@@ -9,8 +9,7 @@ import it.
 Parity status: PINNED.  `tests/golden/make_golden.py` imports the reference's
 `Code/models/unet.py` (authoring container only) and records its outputs on
 deterministic inputs; `tests/test_oracle_golden.py` checks this restatement
-against those committed vectors (<= 1e-6 relative) and, when /root/reference is
-present, against the live reference module.  Dataset-level AUC (README
+against those committed vectors (<= 1e-6 relative).  Dataset-level AUC (README
 screenshots) is unpinned: no checkpoints or data exist.
 
 Each function cites the reference lines it follows (paths relative to

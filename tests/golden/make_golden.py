@@ -197,6 +197,24 @@ def unet_eval(ref, hw, batch, name):
     print(name, y.shape)
 
 
+def twostream_nonsquare(ref, name="twostream_32x48_b1_eval"):
+    """a small NON-SQUARE frame (32x48, batch 1) through the reference's dual-stream network: the parameters and clips
+    of tests/test_oracle_golden.py::test_oracle_vs_live_reference (tag "live"), every output stored whole.  In float64:
+    fp32 CPU convolutions round differently from one processor to the next (~1e-6 of the max at this frame size), the
+    float64 ones agree to ~1e-15"""
+    sd = S.make_twostream_state(tag="live")
+    net = ref.get_twostream((12, 6), (3, 2), 64, 256, 2)
+    net.load_state_dict(sd, strict=True)
+    net.eval().double()
+    rgb_x, op_x, _, _ = S.make_clips(1, 32, 48, tag="live")
+    with torch.no_grad():
+        rgb, op, (rd, od), (rq, oq) = net(rgb_x.double(), op_x.double())
+    np.savez_compressed(os.path.join(HERE, f"{name}.npz"), rgb=rgb.numpy(), op=op.numpy(), rgb_diff=rd.numpy(),
+                        op_diff=od.numpy(), rgb_q=rq.numpy(), op_q=oq.numpy(),
+                        cfg=np.array(json.dumps(dict(h=32, w=48, batch=1, tag="live", n_embed=256, k=2, dtype="float64"))))
+    print(name, rgb.shape, op.shape)
+
+
 def quantize_cases(ref, name="quantize_cases"):
     """`Quantize_topk` alone: shipped shape, cfg2 (2000 slots), cfg5-like (512-d, 8192 slots),
     a deliberate near-tie case, and one training step (EMA buffers)."""
@@ -576,6 +594,9 @@ def main():
         # and a few minutes on 8 cores, so it is made on request only
         twostream_train(ref, 256, 32, "twostream_256_b32_train", out_step=4, rows=(0, 31), dense_samples=4096)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "nonsquare":
+        twostream_nonsquare(ref)
+        return
     param_counts(ref)
     shipped_record_structure()
     quantize_cases(ref)
@@ -583,6 +604,7 @@ def main():
     twostream_eval(ref, 64, 2, 256, "twostream_64_b2_eval", full=True)
     twostream_eval(ref, 64, 2, 2000, "twostream_64_b2_m2000_eval", full=True)
     twostream_eval(ref, 256, 2, 256, "twostream_256_b2_eval", full=False)
+    twostream_nonsquare(ref)
     # the benchmark's own workload (BASELINE.json configs[1]): batch 16, 256x256, 2000 slots
     twostream_eval(ref, 256, 16, 2000, "twostream_256_b16_m2000_eval", full=False, rows=(0, 7, 15), q_step=4, grid=8)
     twostream_train(ref, 64, 2, "twostream_64_b2_train", dense_samples=4096)

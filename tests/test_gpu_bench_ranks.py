@@ -27,7 +27,7 @@ UNITS = {"infer": 4, "train": 2, "stress": 2 * 1024}
 
 
 @pytest.mark.parametrize("launcher", ["torchrun", "self"])
-@pytest.mark.parametrize("mode,extra", [("infer", ["--batch", "4", "--size", "64", "--no-cpu-baseline"]),
+@pytest.mark.parametrize("mode,extra", [("infer", ["--batch", "4", "--size", "64", "--no-cpu-baseline", "--full"]),
                                          ("train", ["--batch", "2", "--size", "64"]),
                                          ("stress", ["--batch", "2"])])
 def test_bench_two_ranks(mode, extra, launcher):

@@ -29,6 +29,7 @@ def _free_port():
 def _worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    torch.cuda.is_available = lambda: False          # the host tier: CPU ranks on a GPU machine too (one GPU has no cuda:1)
     r, w, dev = P.init_distributed("gloo")
     assert (r, w, dev.type) == (rank, world, "cpu")
     # --- reducer: tensors of odd sizes, several buckets, values depend on the rank
