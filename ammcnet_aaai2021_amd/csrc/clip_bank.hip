@@ -1,0 +1,120 @@
+// Device-resident clip bank of the training loop (pipeline.ClipBank, run_train.py): every frame of the training set is
+// decoded once per run, resized once into the bank, and each iteration's clips are gathered from it by one launch.
+//
+// The bank holds exactly what the reference's per-clip arithmetic (two_stream_dataset.py:307-333) depends on, so a
+// gathered clip is bit-identical to `frames_u8_kernel` / `flows_kernel` (pipeline.hip) on the same frame:
+//   rgb bank: uint8 [N][3][H][W], the 8-bit fixed-point resize result `v` (planar, RGB order); the float a clip
+//             holds is a function of `v` alone (`normalize_u8`), a quarter of the fp32 bytes.
+//   op bank : float32 [N][H][W], channel 0 of `_load_op` (`c0 = u / H`); channel 1 is `c0 / W` (:329-330), derived at
+//             gather time as `flows_kernel` derives it.
+#include "resize_common.h"
+
+namespace ammc_impl {
+
+__global__ __launch_bounds__(256) void frames_resize_u8_kernel(const uint8_t* __restrict__ src, int n, int h, int w,
+                                                               uint8_t* __restrict__ dst, int oh, int ow, int bgr,
+                                                               double sx, double sy) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n * oh * ow) return;
+  const int dx = (int)(gid % ow);
+  const int dy = (int)((gid / ow) % oh);
+  const int f = (int)(gid / ((int64_t)ow * oh));
+  const uint8_t* img = src + (int64_t)f * h * w * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int co = bgr ? 2 - c : c;
+    dst[(((int64_t)f * 3 + co) * oh + dy) * ow + dx] = (uint8_t)resize_u8_px(img, h, w, dx, dy, sx, sy, c);
+  }
+}
+
+__global__ __launch_bounds__(256) void flows_resize_c0_kernel(const float* __restrict__ src, int n, int h, int w,
+                                                              float* __restrict__ dst, int oh, int ow, double sx,
+                                                              double sy) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n * oh * ow) return;
+  const int dx = (int)(gid % ow);
+  const int dy = (int)((gid / ow) % oh);
+  const int f = (int)(gid / ((int64_t)ow * oh));
+  dst[((int64_t)f * oh + dy) * ow + dx] = resize_flow_c0(src + (int64_t)f * h * w * 2, h, w, dx, dy, sx, sy, oh);
+}
+
+// One launch per iteration.  blockIdx.y = (sample b, source plane r): r < rgb_len * 3 is (frame, channel) of the rgb
+// clip, the rest one op frame (its c0 plane becomes the clip's two channels).  Each thread moves 4 pixels: a uchar4 /
+// float4 load, 16-byte stores.  A first index outside [0, n - len] (the host validates them all, this is the last line)
+// reads nothing and writes NaN, so a bad index can never reach outside the banks.
+__global__ __launch_bounds__(256) void gather_clips_kernel(const uint8_t* __restrict__ rgb_bank, int64_t n_rgb,
+                                                           const float* __restrict__ op_bank, int64_t n_op,
+                                                           const int32_t* __restrict__ rgb_first,
+                                                           const int32_t* __restrict__ op_first, int rgb_len,
+                                                           int op_len, int h, int w, float* __restrict__ rgb_out,
+                                                           float* __restrict__ op_out) {
+  const int64_t hw = (int64_t)h * w;
+  const int64_t q = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (q >= hw) return;
+  const int planes = rgb_len * 3 + op_len;
+  const int b = (int)blockIdx.y / planes, r = (int)blockIdx.y % planes;
+  const float nan = __builtin_nanf("");
+  if (r < rgb_len * 3) {
+    const int t = r / 3, c = r % 3;
+    const int64_t first = rgb_first[b];
+    float4 o = make_float4(nan, nan, nan, nan);
+    if (first >= 0 && first + rgb_len <= n_rgb) {
+      const uchar4 v = *reinterpret_cast<const uchar4*>(rgb_bank + ((first + t) * 3 + c) * hw + q);
+      o = make_float4(normalize_u8(v.x), normalize_u8(v.y), normalize_u8(v.z), normalize_u8(v.w));
+    }
+    *reinterpret_cast<float4*>(rgb_out + (((int64_t)b * rgb_len + t) * 3 + c) * hw + q) = o;
+  } else {
+    const int t = r - rgb_len * 3;
+    const int64_t first = op_first[b];
+    float4 c0 = make_float4(nan, nan, nan, nan), c1 = c0;
+    if (first >= 0 && first + op_len <= n_op) {
+      c0 = *reinterpret_cast<const float4*>(op_bank + (first + t) * hw + q);
+      c1 = make_float4(flow_c1(c0.x, w), flow_c1(c0.y, w), flow_c1(c0.z, w), flow_c1(c0.w, w));
+    }
+    float* dst = op_out + (((int64_t)b * op_len + t) * 2) * hw + q;
+    *reinterpret_cast<float4*>(dst) = c0;
+    *reinterpret_cast<float4*>(dst + hw) = c1;
+  }
+}
+
+}  // namespace ammc_impl
+using namespace ammc_impl;
+
+extern "C" int ammc_frames_u8_resize_u8(const uint8_t* src, int32_t n, int32_t h, int32_t w, uint8_t* dst, int32_t oh,
+                                        int32_t ow, int32_t bgr, void* stream) {
+  if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return AMMC_EINVAL;
+  const int64_t total = (int64_t)n * oh * ow;
+  if ((total + 255) / 256 > 0x7fffffff) return AMMC_EINVAL;
+  hipLaunchKernelGGL(frames_resize_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     src, n, h, w, dst, oh, ow, bgr ? 1 : 0, (double)w / (double)ow, (double)h / (double)oh);
+  return ammc_launch_status();
+}
+
+extern "C" int ammc_flows_resize_c0(const float* src, int32_t n, int32_t h, int32_t w, float* dst, int32_t oh,
+                                    int32_t ow, void* stream) {
+  if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return AMMC_EINVAL;
+  const int64_t total = (int64_t)n * oh * ow;
+  if ((total + 255) / 256 > 0x7fffffff) return AMMC_EINVAL;
+  hipLaunchKernelGGL(flows_resize_c0_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     src, n, h, w, dst, oh, ow, (double)w / (double)ow, (double)h / (double)oh);
+  return ammc_launch_status();
+}
+
+extern "C" int ammc_gather_clips(const uint8_t* rgb_bank, int64_t n_rgb, const float* op_bank, int64_t n_op,
+                                 const int32_t* rgb_first, const int32_t* op_first, int32_t batch, int32_t rgb_len,
+                                 int32_t op_len, int32_t h, int32_t w, float* rgb_out, float* op_out, void* stream) {
+  if (!rgb_bank || !op_bank || !rgb_first || !op_first || !rgb_out || !op_out) return AMMC_EINVAL;
+  if (batch <= 0 || rgb_len <= 0 || op_len <= 0 || h <= 0 || w <= 0 || n_rgb < rgb_len || n_op < op_len)
+    return AMMC_EINVAL;
+  const int64_t hw = (int64_t)h * w;
+  if (hw % 4 != 0) return AMMC_EINVAL;                                  // 4 pixels per thread, 16-byte aligned planes
+  if (((uintptr_t)rgb_bank & 3) || ((uintptr_t)op_bank & 15) || ((uintptr_t)rgb_out & 15) || ((uintptr_t)op_out & 15))
+    return AMMC_EINVAL;
+  const int64_t grid_y = (int64_t)batch * ((int64_t)rgb_len * 3 + op_len);
+  const int64_t grid_x = (hw / 4 + 255) / 256;
+  if (grid_y > 65535 || grid_x > 0x7fffffff) return AMMC_EINVAL;
+  hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)grid_x, (unsigned)grid_y), dim3(256), 0, (hipStream_t)stream,
+                     rgb_bank, n_rgb, op_bank, n_op, rgb_first, op_first, (int)rgb_len, (int)op_len, (int)h, (int)w,
+                     rgb_out, op_out);
+  return ammc_launch_status();
+}

@@ -382,11 +382,14 @@ def generator_loss_full(out, rgb_t, op_t, d_gen, flow_pred=None, flow_gt=None, l
 
 
 def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, optimizer_G, optimizer_D,
-                   rgb: torch.Tensor, op: torch.Tensor, flow_fn: Optional[Callable] = None, **lams):
+                   rgb: torch.Tensor, op: torch.Tensor, flow_fn: Optional[Callable] = None,
+                   outputs: Optional[dict] = None, **lams):
     """One iteration of the joint loop (train_helper.py:296-339): G forward, D(G(x)) for the adversarial term, the D
     update on (target, detached prediction), then the G update.  The gradient that reaches G through D uses the
     filters D had when `d_gen` was computed (before its update), i.e. the exact derivative of the loss value.
-    `flow_fn(prev_frame, frame) -> flow` stands in for FlowNet2-SD when given."""
+    `flow_fn(prev_frame, frame) -> flow` stands in for FlowNet2-SD when given.  `outputs`: a dict that receives the
+    detached predicted frames ("rgb", "op"; the train PSNR of the reference's log, train_helper.py:355-357) - they may
+    alias the engine's buffers, so read them before the next iteration is enqueued."""
     b = rgb.shape[0]
     rgb_in = rgb[:, :-1].reshape(b, -1, *rgb.shape[-2:])
     op_in = op[:, :-1].reshape(b, -1, *op.shape[-2:])
@@ -455,6 +458,8 @@ def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, o
     optimizer_G.step()
     if overlap:
         main.wait_stream(lane)                     # successors on the caller's stream see both updates
+    if outputs is not None:
+        outputs["rgb"], outputs["op"] = out[0].detach(), out[1].detach()
     return g_loss.detach(), d_loss.detach()
 
 

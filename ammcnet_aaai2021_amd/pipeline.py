@@ -210,3 +210,255 @@ class SubVideoStager:
             yield rgb, op
             del keep
         th.join()
+
+
+# ---- training: the device-resident clip bank and the reference's draw rule ------------------------------------------
+
+class ClipSampler:
+    """The reference's training draw (`TwoStream_Train_DS.__getitem__`, two_stream_dataset.py:467-468, over
+    `clip_Train_DS.__getitem__`, :289-292) as it runs with `num_workers=0`: one `np.random.RandomState(seed)` (the
+    module-level `rng = RandomState(2017)` of :31) and, per sample, in this order:
+
+      1. rgb: `vid = randint(0, n_rgb_videos)`, then `start = randint(0, len(vid) - rgb_len)`;
+      2. op:  `vid = randint(0, n_op_videos)`,  then `start = randint(0, len(vid) - op_len)`.
+
+    Two quirks of the reference are kept as it runs them: the rgb and op clips of a sample are drawn INDEPENDENTLY (other
+    videos, other starts), and the upper bound of `randint` is exclusive, so a video's last clip (start len - clip_len) is
+    never drawn.  One artefact is NOT reproduced: the reference trains with 16 DataLoader workers, each a fork that copies
+    the module-level RNG, so the workers' draw streams repeat each other; here one stream feeds every sample.
+
+    `rgb_lens` / `op_lens`: frames per sub-video of each folder (sorted order).  `draw(b)` returns the four int arrays
+    (rgb video, rgb start, op video, op start)."""
+
+    def __init__(self, rgb_lens: Sequence[int], op_lens: Sequence[int], rgb_len: int = 5, op_len: int = 4,
+                 seed: int = 2017):
+        self.rgb_lens, self.op_lens = [int(n) for n in rgb_lens], [int(n) for n in op_lens]
+        self.rgb_len, self.op_len = int(rgb_len), int(op_len)
+        if not self.rgb_lens or not self.op_lens:
+            raise ValueError("ClipSampler: no sub-videos")
+        for what, lens, clip in (("rgb", self.rgb_lens, self.rgb_len), ("op", self.op_lens, self.op_len)):
+            short = [i for i, n in enumerate(lens) if n <= clip]
+            if short:
+                raise ValueError(f"ClipSampler: {what} sub-videos {short} have <= {clip} frames: the draw rule needs "
+                                 f"at least {clip + 1}")
+        self.rng = np.random.RandomState(seed)
+
+    def draw(self, batch: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        out = np.empty((4, batch), np.int64)
+        r = self.rng
+        for i in range(batch):
+            v = r.randint(0, len(self.rgb_lens))
+            out[0, i], out[1, i] = v, r.randint(0, self.rgb_lens[v] - self.rgb_len)
+            v = r.randint(0, len(self.op_lens))
+            out[2, i], out[3, i] = v, r.randint(0, self.op_lens[v] - self.op_len)
+        return out[0], out[1], out[2], out[3]
+
+    def get_state(self) -> dict:
+        """the RNG state as plain values and a tensor (loadable with `torch.load(weights_only=True)`)"""
+        name, keys, pos, has_gauss, cached = self.rng.get_state()
+        return {"name": name, "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos),
+                "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+
+    def set_state(self, st: dict) -> None:
+        keys = st["keys"].numpy() if isinstance(st["keys"], torch.Tensor) else np.asarray(st["keys"])
+        self.rng.set_state((st["name"], keys.astype(np.uint32), int(st["pos"]), int(st["has_gauss"]),
+                            float(st["cached_gaussian"])))
+
+
+def _size_wh(size) -> Tuple[int, int]:
+    """`size` as (width, height): an int is a square"""
+    if isinstance(size, int):
+        return size, size
+    w, h = size
+    return int(w), int(h)
+
+
+def bank_bytes(n_rgb_frames: int, n_op_frames: int, size) -> int:
+    """device bytes of a ClipBank: uint8 [N][3][H][W] + float32 [N'][H][W]"""
+    w, h = _size_wh(size)
+    return n_rgb_frames * 3 * h * w + n_op_frames * 4 * h * w
+
+
+class ClipBank:
+    """Every frame of a training set, decoded once and resized once into device memory; each iteration's clips gathered
+    from it by one launch (`csrc/clip_bank.hip`), bit-identical to `frames_to_device` / `flows_to_device`.
+
+    Layout: `rgb` uint8 [N][3][H][W] holds the 8-bit resize result (the normalised float is a function of it alone, a
+    quarter of the bytes); `op` float32 [N'][H][W] holds channel 0 of `_load_op` (`u / H`), channel 1 (`c0 / W`) is
+    derived at gather time.  Sub-video v occupies frames [rgb_start[v], rgb_start[v] + rgb_count[v]) (op likewise);
+    `gather` takes GLOBAL first-frame indices and validates every one of them on the host (a clip never crosses a
+    sub-video) before anything is launched.
+
+    Filling: sub-videos from `list_subvideos` (sorted); the bank size is estimated from the file counts and the fill
+    refused BEFORE anything is decoded when it exceeds `budget_gb` (default: 80 % of the device's free memory).  Frames
+    are decoded by a pool of `workers` threads (PIL releases the GIL) into pinned staging buffers (two, alternating,
+    each guarded by an event so it is not rewritten before its copy ran), copied to the device at their native
+    resolution (which may differ between sub-videos) and resized into the sub-video's slice on a side stream.
+    `fill_seconds`: wall time of the whole fill."""
+
+    def __init__(self, rgb_root: str, op_root: str, size, device, workers: int = 8, budget_gb: Optional[float] = None,
+                 rgb_len: int = 5, op_len: int = 4, bgr: bool = False):
+        import time
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.AmmcHipError("ClipBank lives on a GPU; there is no CPU pipeline")
+        self.width, self.height = _size_wh(size)
+        if (self.width * self.height) % 4:
+            raise _lib.AmmcHipError(f"ClipBank: {self.width}x{self.height} frames: the gather needs H * W % 4 == 0")
+        self.rgb_len, self.op_len, self.bgr, self.workers = int(rgb_len), int(op_len), bool(bgr), max(1, int(workers))
+        self.videos = list_subvideos(rgb_root, op_root)
+        if not self.videos:
+            raise ValueError(f"ClipBank: no sub-video folders under {rgb_root}")
+        self.rgb_count = np.array([len(f) for f, _ in self.videos], np.int64)
+        self.op_count = np.array([len(o) for _, o in self.videos], np.int64)
+        self.rgb_start = np.concatenate([[0], np.cumsum(self.rgb_count)[:-1]]).astype(np.int64)
+        self.op_start = np.concatenate([[0], np.cumsum(self.op_count)[:-1]]).astype(np.int64)
+        self.n_rgb, self.n_op = int(self.rgb_count.sum()), int(self.op_count.sum())
+        self.nbytes = bank_bytes(self.n_rgb, self.n_op, (self.width, self.height))
+        if budget_gb is None:
+            free, _ = torch.cuda.mem_get_info(self.device)
+            budget, whose = 0.8 * free, f"80 % of the {free / 1e9:.2f} GB free on {self.device}"
+        else:
+            budget, whose = float(budget_gb) * 1e9, f"the budget of {float(budget_gb):.2f} GB"
+        if self.nbytes > budget:
+            raise _lib.AmmcHipError(
+                f"ClipBank: {self.n_rgb} frames + {self.n_op} flows at {self.width}x{self.height} need "
+                f"{self.nbytes / 1e9:.2f} GB of device memory, more than {whose}")
+        if max(self.n_rgb, self.n_op) >= 2**31:
+            raise _lib.AmmcHipError("ClipBank: more than 2^31 frames (the gather's indices are int32)")
+        t0 = time.perf_counter()
+        self.rgb = torch.empty(self.n_rgb, 3, self.height, self.width, dtype=torch.uint8, device=self.device)
+        self.op = torch.empty(max(self.n_op, 1), self.height, self.width, dtype=torch.float32, device=self.device)
+        self._fill()
+        self.fill_seconds = time.perf_counter() - t0
+        self._idx_pinned = [torch.empty(0, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self._idx_events = [None, None]
+        self._idx_turn = 0
+
+    # -- fill ----------------------------------------------------------------------------------------------------------
+
+    def _fill(self) -> None:
+        from concurrent.futures import ThreadPoolExecutor
+        stream = torch.cuda.Stream(self.device)
+        staging = {}                                          # (kind, slot) -> (pinned tensor, event of its last copy)
+        lib = _lib.load()
+
+        def stage(kind, slot, shape, dtype):
+            buf, ev = staging.get((kind, slot), (None, None))
+            if ev is not None:
+                ev.synchronize()                              # its previous copy has run: the buffer may be rewritten
+            n = int(np.prod(shape))
+            if buf is None or buf.numel() < n:
+                buf = torch.empty(n, dtype=dtype).pin_memory()
+            staging[(kind, slot)] = (buf, None)
+            return buf[:n].view(*shape)
+
+        def upload(kind, slot, host):
+            with torch.cuda.stream(stream):
+                dev = host.to(self.device, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(stream)
+            staging[(kind, slot)] = (staging[(kind, slot)][0], ev)
+            return dev
+
+        with ThreadPoolExecutor(self.workers) as pool:
+            for v, (frames, flows) in enumerate(self.videos):
+                slot = v % 2
+                if frames:
+                    imgs = list(pool.map(read_image, frames))
+                    h, w = imgs[0].shape[:2]
+                    if any(im.shape != (h, w, 3) for im in imgs):
+                        raise ValueError(f"ClipBank: frames of different sizes in {os.path.dirname(frames[0])}")
+                    host = stage("rgb", slot, (len(imgs), h, w, 3), torch.uint8)
+                    pool_np = host.numpy()
+                    for i, im in enumerate(imgs):
+                        pool_np[i] = im
+                    dev = upload("rgb", slot, host)
+                    s0 = int(self.rgb_start[v])
+                    with torch.cuda.stream(stream):
+                        _lib.check(lib.ammc_frames_u8_resize_u8(dev.data_ptr(), len(imgs), h, w, self.rgb[s0].data_ptr(),
+                                                                self.height, self.width, int(self.bgr), stream.cuda_stream),
+                                   "frames_u8_resize_u8")
+                        dev.record_stream(stream)
+                if flows:
+                    fls = list(pool.map(_read_flow_file, flows))
+                    h, w = fls[0].shape[:2]
+                    if any(f.shape != (h, w, 2) for f in fls):
+                        raise ValueError(f"ClipBank: flows of different sizes in {os.path.dirname(flows[0])}")
+                    host = stage("op", slot, (len(fls), h, w, 2), torch.float32)
+                    pool_np = host.numpy()
+                    for i, f in enumerate(fls):
+                        pool_np[i] = f
+                    dev = upload("op", slot, host)
+                    s0 = int(self.op_start[v])
+                    with torch.cuda.stream(stream):
+                        _lib.check(lib.ammc_flows_resize_c0(dev.data_ptr(), len(fls), h, w, self.op[s0].data_ptr(),
+                                                            self.height, self.width, stream.cuda_stream), "flows_resize_c0")
+                        dev.record_stream(stream)
+        stream.synchronize()
+        torch.cuda.current_stream(self.device).wait_stream(stream)
+
+    # -- gather --------------------------------------------------------------------------------------------------------
+
+    def global_index(self, rgb_vid, rgb_start, op_vid, op_start) -> Tuple[np.ndarray, np.ndarray]:
+        """(sub-video, start) pairs (`ClipSampler.draw`) -> global first-frame indices of the banks"""
+        return (self.rgb_start[np.asarray(rgb_vid)] + np.asarray(rgb_start),
+                self.op_start[np.asarray(op_vid)] + np.asarray(op_start))
+
+    def validate(self, rgb_first, op_first) -> Tuple[np.ndarray, np.ndarray]:
+        """host check of every index (`check_clip_indices`); raises AmmcHipError"""
+        rf = check_clip_indices("rgb", rgb_first, self.rgb_start, self.rgb_count, self.rgb_len)
+        of = check_clip_indices("op", op_first, self.op_start, self.op_count, self.op_len)
+        if rf.size != of.size or rf.size == 0:
+            raise _lib.AmmcHipError("ClipBank.gather: need as many (>= 1) rgb as op indices")
+        return rf, of
+
+    def gather(self, rgb_first, op_first) -> Tuple[torch.Tensor, torch.Tensor]:
+        """host int arrays of global first frames -> (rgb float32 [B, rgb_len, 3, H, W], op float32 [B, op_len, 2, H, W])
+        on the current stream: the indices go H2D through one of two pinned buffers (event-guarded), then one launch"""
+        rf, of = self.validate(rgb_first, op_first)
+        b = rf.size
+        k = self._idx_turn
+        self._idx_turn ^= 1
+        if self._idx_events[k] is not None:
+            self._idx_events[k].synchronize()                 # the copy that last read this buffer has run
+        if self._idx_pinned[k].numel() < 2 * b:
+            self._idx_pinned[k] = torch.empty(2 * b, dtype=torch.int32).pin_memory()
+        host = self._idx_pinned[k][:2 * b].view(2, b)
+        hn = host.numpy()
+        hn[0], hn[1] = rf, of
+        stream = torch.cuda.current_stream(self.device)
+        idx = torch.empty(2, b, dtype=torch.int32, device=self.device)
+        idx.copy_(host, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._idx_events[k] = ev
+        rgb = torch.empty(b, self.rgb_len, 3, self.height, self.width, dtype=torch.float32, device=self.device)
+        op = torch.empty(b, self.op_len, 2, self.height, self.width, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().ammc_gather_clips(self.rgb.data_ptr(), self.n_rgb, self.op.data_ptr(), self.n_op,
+                                                 idx[0].data_ptr(), idx[1].data_ptr(), b, self.rgb_len, self.op_len,
+                                                 self.height, self.width, rgb.data_ptr(), op.data_ptr(), stream.cuda_stream),
+                   "gather_clips")
+        return rgb, op
+
+
+def check_clip_indices(what: str, first, starts: np.ndarray, counts: np.ndarray, clip: int) -> np.ndarray:
+    """global first-frame indices of clips of `clip` frames in a bank whose sub-video v holds frames
+    [starts[v], starts[v] + counts[v]): every clip must start inside a sub-video and end inside THE SAME one; returns
+    them as int64, raises AmmcHipError naming the first bad clip"""
+    a = np.asarray(first).reshape(-1)
+    if a.dtype.kind not in "iu":
+        raise _lib.AmmcHipError(f"ClipBank.gather: {what} indices must be integers, got {a.dtype}")
+    a = a.astype(np.int64)
+    v = np.searchsorted(starts, a, side="right") - 1
+    vc = np.clip(v, 0, len(starts) - 1)
+    ok = (a >= 0) & (v >= 0) & (a + clip <= starts[vc] + counts[vc])
+    if not ok.all():
+        bad = int(np.flatnonzero(~ok)[0])
+        raise _lib.AmmcHipError(f"ClipBank.gather: {what} clip {bad} (first frame {int(a[bad])}, {clip} frames) does not "
+                                f"lie inside one sub-video of the bank")
+    return a
+
+
+def _read_flow_file(p: str) -> np.ndarray:
+    return read_flo(p) if p.endswith(".flo") else np.load(p).astype(np.float32)

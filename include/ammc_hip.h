@@ -424,6 +424,24 @@ int ammc_frames_u8_to_f32(const uint8_t* src, int32_t n, int32_t h, int32_t w, f
 int ammc_flows_to_f32(const float* src, int32_t n, int32_t h, int32_t w, float* dst, int32_t oh, int32_t ow,
                       void* stream);
 
+/* Clip bank of the training loop (pipeline.ClipBank): each frame resized once into a device-resident bank, each
+ * iteration's clips gathered from it by one launch, bit-identical to the two entries above.
+ * frames: as ammc_frames_u8_to_f32, stopping before the normalisation: the 8-bit resize result, uint8 [n][3][oh][ow]
+ *   (RGB order).
+ * flows: as ammc_flows_to_f32, channel 0 only: c0 = u / oh, float32 [n][oh][ow].
+ * gather: clip b = bank frames [rgb_first[b], + rgb_len) and [op_first[b], + op_len) (device int32 [batch] each) ->
+ *   rgb_out float32 [batch][rgb_len][3][h][w] = (v / 255 - 0.5) / 0.5, op_out float32 [batch][op_len][2][h][w] =
+ *   (c0, c0 / w).  n_rgb / n_op: frames in the banks.  Needs h * w % 4 == 0, rgb_bank 4-byte and op_bank / outputs
+ *   16-byte aligned, batch * (3 rgb_len + op_len) <= 65535; AMMC_EINVAL otherwise.  The caller validates the indices
+ *   (a clip never crosses a sub-video); a clip whose index is outside [0, n - len] is written as NaN, nothing is read. */
+int ammc_frames_u8_resize_u8(const uint8_t* src, int32_t n, int32_t h, int32_t w, uint8_t* dst, int32_t oh, int32_t ow,
+                             int32_t bgr, void* stream);
+int ammc_flows_resize_c0(const float* src, int32_t n, int32_t h, int32_t w, float* dst, int32_t oh, int32_t ow,
+                         void* stream);
+int ammc_gather_clips(const uint8_t* rgb_bank, int64_t n_rgb, const float* op_bank, int64_t n_op, const int32_t* rgb_first,
+                      const int32_t* op_first, int32_t batch, int32_t rgb_len, int32_t op_len, int32_t h, int32_t w,
+                      float* rgb_out, float* op_out, void* stream);
+
 /* nn.BatchNorm2d in training mode (unet.py:12,15).  Per-channel reductions write
  * partial[ammc_chan_reduce_blocks(B*H*W)][Q][C]; the finalizers combine them in fp64, fixed order. */
 int ammc_chan_reduce_blocks(int32_t pixels);
