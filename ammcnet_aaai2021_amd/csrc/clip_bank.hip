@@ -77,6 +77,42 @@ __global__ __launch_bounds__(256) void gather_clips_kernel(const uint8_t* __rest
   }
 }
 
+// The clips of ONE bank (a single-stream training stage: rgb or op only), the same scheme as `gather_clips_kernel`:
+// blockIdx.y = (sample b, source plane r) of that bank alone, so every clip is written by the same arithmetic as the
+// matching half of `gather_clips_kernel` - bit-identical for the same indices.  `op` selects the bank: 0 = rgb (uint8
+// [N][3][H][W] -> normalised float, 3 planes per frame), 1 = op (c0 float [N][H][W] -> (c0, c0 / w), 1 plane per frame).
+__global__ __launch_bounds__(256) void gather_clips_one_kernel(const void* __restrict__ bank, int64_t n, int op,
+                                                               const int32_t* __restrict__ first_idx, int len, int h,
+                                                               int w, float* __restrict__ out) {
+  const int64_t hw = (int64_t)h * w;
+  const int64_t q = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (q >= hw) return;
+  const int planes = op ? len : len * 3;
+  const int b = (int)blockIdx.y / planes, r = (int)blockIdx.y % planes;
+  const int64_t first = first_idx[b];
+  const bool ok = first >= 0 && first + len <= n;
+  const float nan = __builtin_nanf("");
+  if (!op) {
+    const int t = r / 3, c = r % 3;
+    float4 o = make_float4(nan, nan, nan, nan);
+    if (ok) {
+      const uchar4 v = *reinterpret_cast<const uchar4*>((const uint8_t*)bank + ((first + t) * 3 + c) * hw + q);
+      o = make_float4(normalize_u8(v.x), normalize_u8(v.y), normalize_u8(v.z), normalize_u8(v.w));
+    }
+    *reinterpret_cast<float4*>(out + (((int64_t)b * len + t) * 3 + c) * hw + q) = o;
+  } else {
+    const int t = r;
+    float4 c0 = make_float4(nan, nan, nan, nan), c1 = c0;
+    if (ok) {
+      c0 = *reinterpret_cast<const float4*>((const float*)bank + (first + t) * hw + q);
+      c1 = make_float4(flow_c1(c0.x, w), flow_c1(c0.y, w), flow_c1(c0.z, w), flow_c1(c0.w, w));
+    }
+    float* dst = out + (((int64_t)b * len + t) * 2) * hw + q;
+    *reinterpret_cast<float4*>(dst) = c0;
+    *reinterpret_cast<float4*>(dst + hw) = c1;
+  }
+}
+
 }  // namespace ammc_impl
 using namespace ammc_impl;
 
@@ -116,5 +152,20 @@ extern "C" int ammc_gather_clips(const uint8_t* rgb_bank, int64_t n_rgb, const f
   hipLaunchKernelGGL(gather_clips_kernel, dim3((unsigned)grid_x, (unsigned)grid_y), dim3(256), 0, (hipStream_t)stream,
                      rgb_bank, n_rgb, op_bank, n_op, rgb_first, op_first, (int)rgb_len, (int)op_len, (int)h, (int)w,
                      rgb_out, op_out);
+  return ammc_launch_status();
+}
+
+extern "C" int ammc_gather_clips_one(const void* bank, int64_t n, int32_t kind, const int32_t* first, int32_t batch,
+                                     int32_t len, int32_t h, int32_t w, float* out, void* stream) {
+  if (!bank || !first || !out || (kind != 0 && kind != 1)) return AMMC_EINVAL;
+  if (batch <= 0 || len <= 0 || h <= 0 || w <= 0 || n < len) return AMMC_EINVAL;
+  const int64_t hw = (int64_t)h * w;
+  if (hw % 4 != 0) return AMMC_EINVAL;                                  // 4 pixels per thread, 16-byte aligned planes
+  if (((uintptr_t)bank & (kind ? 15 : 3)) || ((uintptr_t)out & 15)) return AMMC_EINVAL;
+  const int64_t grid_y = (int64_t)batch * (kind ? len : (int64_t)len * 3);
+  const int64_t grid_x = (hw / 4 + 255) / 256;
+  if (grid_y > 65535 || grid_x > 0x7fffffff) return AMMC_EINVAL;
+  hipLaunchKernelGGL(gather_clips_one_kernel, dim3((unsigned)grid_x, (unsigned)grid_y), dim3(256), 0,
+                     (hipStream_t)stream, bank, n, (int)kind, first, (int)len, (int)h, (int)w, out);
   return ammc_launch_status();
 }

@@ -480,6 +480,143 @@ def _gan_side_stream(device, which: int = 0) -> "torch.cuda.Stream":
     return _GAN_LANES[key]
 
 
+# ---- stage 1 of the reference's recipe: one stream (`UNetMem_v7`) trained on its own ---------------------------------
+
+SINGLE_LAMS = {"rgb": dict(lam_adv=0.05, lam_gdl=1.0, lam_flow=2.0, lam_lp=1.0, lam_latent=1.0),
+               "op": dict(lam_lp_op=1.0, lam_adv_op=0.0, lam_latent=1.0)}
+"""the loss weights of each single-stream stage and their defaults (the values of LAMS_ANOPRED; `lam_adv_op` lives in
+a per-dataset .ini that is not shipped, and the README's stage 1 is prediction + commit loss only: 0 = no discriminator)"""
+
+
+def clip_stream(clips: torch.Tensor) -> str:
+    """"rgb" / "op" from a clip batch [B, T, c, H, W] (3 channels: frames, 2: flows)"""
+    if clips.dim() != 5 or clips.shape[2] not in (2, 3):
+        raise ValueError(f"expected clips [B, T, 3 or 2, H, W], got {tuple(clips.shape)}")
+    return "rgb" if clips.shape[2] == 3 else "op"
+
+
+def single_stream_loss(stream: str, pred, target, diff, d_gen=None, flow_pred=None, flow_gt=None, **lams):
+    """`rgb_vq_Loss` (loss_zoo.py:101-137): lam_adv adv + lam_gdl gdl + lam_flow flow + lam_lp int + lam_latent latent,
+    or `op_vq_Loss` (:171-198): lam_lp_op int + lam_adv_op adv + lam_latent latent - the adversarial term only where a
+    discriminator output `d_gen` is given, the flow term only where flows are.  `int` is the channel-L2 intensity loss
+    of `generator_loss`, `latent` the commit loss `diff`.  -> (loss, {term: unweighted value})"""
+    unknown = set(lams) - set(SINGLE_LAMS[stream])
+    if unknown:
+        raise TypeError(f"the {stream} stage has no loss weight {sorted(unknown)} (it takes {sorted(SINGLE_LAMS[stream])})")
+    lam = {**SINGLE_LAMS[stream], **lams}
+    t = {"int": torch.norm(pred - target, p=2, dim=1).mean(), "latent": diff.sum()}
+    if stream == "rgb":
+        if d_gen is None:
+            raise ValueError("the rgb stage's loss has an adversarial term: it needs the discriminator's output")
+        t["adv"], t["gdl"] = adversarial_loss(d_gen), gradient_loss(pred, target)
+        loss = lam["lam_adv"] * t["adv"] + lam["lam_gdl"] * t["gdl"]
+        if flow_pred is not None:
+            t["flow"] = flow_loss(flow_pred, flow_gt)
+            loss = loss + lam["lam_flow"] * t["flow"]
+        loss = loss + lam["lam_lp"] * t["int"]
+    else:
+        loss = lam["lam_lp_op"] * t["int"]
+        if d_gen is not None:
+            t["adv"] = adversarial_loss(d_gen)
+            loss = loss + lam["lam_adv_op"] * t["adv"]
+    return loss + lam["lam_latent"] * t["latent"], t
+
+
+def train_step_single_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, optimizer_G, optimizer_D,
+                          clips: torch.Tensor, flow_fn: Optional[Callable] = None, outputs: Optional[dict] = None, **lams):
+    """One iteration of a single-stream stage with its discriminator (`inference_v3` / `inference_v4`,
+    train_helper.py:1592-1766): `generator` a `UNetMem_v7`, `clips` [B, T, c, H, W] with the target last - frames (the
+    rgb stage, c = 3, `rgb_vq_Loss`; `flow_fn` stands in for FlowNet2-SD as in `train_step_gan`, both pairs starting
+    from the target) or flows (the op stage with lam_adv_op > 0, c = 2, `op_vq_Loss`; no flow term).  The same
+    schedule as `train_step_gan`: D(real || fake) as one call, D updated first (on the `AMMC_GAN_OVERLAP` lane), G
+    through D with the pre-step filters, then the G update; the verdict of `_FiniteWatch` covers both losses and the S16
+    range flags of D and of the flow network.  Returns the detached (g_loss, d_loss); `outputs` receives the detached
+    prediction ("pred") and the loss terms ("terms", unweighted) - read them before the next iteration is enqueued."""
+    b = clips.shape[0]
+    stream = clip_stream(clips)
+    if flow_fn is not None and stream != "rgb":
+        raise ValueError("the flow term belongs to the rgb stage")
+    x = clips[:, :-1].reshape(b, -1, *clips.shape[-2:])
+    target = clips[:, -1]
+    pred, diff, _ = generator(x)
+    vote, group = _watch_group(generator, discriminator)
+    overlap = GAN_OVERLAP and pred.is_cuda and not vote and getattr(discriminator, "_grad_reducer", None) is None
+    main = torch.cuda.current_stream(pred.device) if overlap else None
+    lane = _gan_side_stream(pred.device) if overlap else None
+
+    def d_forward():
+        d_both_ = discriminator(torch.cat([target, pred.detach()]))      # D(real) and D(fake.detach()) as one call
+        return d_both_, discriminate_loss(d_both_[:b], d_both_[b:]), getattr(discriminator, "last_overflow", None)
+    early = overlap and GAN_OVERLAP_EARLY
+    if early:
+        lane.wait_stream(main)
+        with torch.cuda.stream(lane):
+            d_both, d_loss, d_flag = d_forward()
+    flow_pred = flow_gt = None
+    flow_mods = [m for m in (getattr(flow_fn, "__self__", None), getattr(flow_fn, "net", None)) if m is not None]
+    if flow_fn is not None:
+        with torch.no_grad():          # (target, prediction) and (target, target), one batch of 2 b pairs
+            both = flow_fn(torch.cat([target, target]), torch.cat([pred.detach(), target]))
+            flow_pred, flow_gt = both[:b], both[b:]
+    d_params = [p for p in discriminator.parameters() if p.requires_grad]
+    for p in d_params:
+        p.requires_grad_(False)
+    try:
+        d_gen = discriminator(pred)
+    finally:
+        for p in d_params:
+            p.requires_grad_(True)
+    g_loss, terms = single_stream_loss(stream, pred, target, diff, d_gen, flow_pred, flow_gt, **lams)
+    if not early:
+        if overlap:
+            lane.wait_stream(main)
+        with (torch.cuda.stream(lane) if overlap else contextlib.nullcontext()):
+            d_both, d_loss, d_flag = d_forward()
+    if overlap:
+        main.wait_stream(lane)
+        for t in (d_both, d_loss) + ((d_flag,) if d_flag is not None else ()):
+            t.record_stream(main)
+    watch = _FiniteWatch(d_loss, g_loss, group=group, vote=vote,
+                         flags=[d_flag] + [getattr(m, "last_overflow", None) for m in flow_mods])
+    with (torch.cuda.stream(lane) if overlap else contextlib.nullcontext()):
+        optimizer_D.zero_grad(set_to_none=True)
+        d_loss.backward()
+        watch.step(optimizer_D)
+    optimizer_G.zero_grad(set_to_none=True)
+    g_loss.backward()
+    optimizer_G.step()
+    if overlap:
+        main.wait_stream(lane)
+    if outputs is not None:
+        outputs["pred"], outputs["terms"] = pred.detach(), {k: v.detach() for k, v in terms.items()}
+    return g_loss.detach(), d_loss.detach()
+
+
+def train_step_single(generator: torch.nn.Module, optimizer_G, clips: torch.Tensor, outputs: Optional[dict] = None,
+                      **lams) -> torch.Tensor:
+    """One iteration of the op stage without a discriminator (lam_adv_op = 0: the README's stage 1, prediction + commit
+    loss, `inference_v4_1` / `op_vq_Loss_v1`, loss_zoo.py:232-262): `clips` flows [B, T, 2, H, W], target last.
+    Returns the detached loss; `outputs` as `train_step_single_gan`'s."""
+    b = clips.shape[0]
+    if clip_stream(clips) != "op":
+        raise ValueError("train_step_single is the discriminator-less op stage: the rgb stage is train_step_single_gan")
+    if lams.get("lam_adv_op", 0.0):
+        raise ValueError("lam_adv_op > 0 needs a discriminator: train_step_single_gan")
+    lams = {k: v for k, v in lams.items() if k != "lam_adv_op"}
+    x = clips[:, :-1].reshape(b, -1, *clips.shape[-2:])
+    target = clips[:, -1]
+    optimizer_G.zero_grad(set_to_none=True)
+    pred, diff, _ = generator(x)
+    loss, terms = single_stream_loss("op", pred, target, diff, **lams)
+    vote, group = _watch_group(generator)
+    watch = _FiniteWatch(loss, group=group, vote=vote)
+    loss.backward()
+    watch.step(optimizer_G)
+    if outputs is not None:
+        outputs["pred"], outputs["terms"] = pred.detach(), {k: v.detach() for k, v in terms.items()}
+    return loss.detach()
+
+
 # ---- score fusion and frame-level AUC (the step after the records) ------------------------------
 
 LAM_MAP = {"avenue": (0.04, 0.65), "ped2": (0.01, 0.55), "shanghaitech": (0.13, 0.60)}   # test_helper.py:565-569

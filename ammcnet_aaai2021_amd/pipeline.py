@@ -59,12 +59,13 @@ def read_image(path: str) -> np.ndarray:
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
 
 
-def list_subvideos(rgb_root: str, op_root: str) -> List[Tuple[List[str], List[str]]]:
-    """sorted sub-video folders, sorted files inside (test_helper.py:404-411, two_stream_dataset.py:515-518)"""
+def list_subvideos(rgb_root: Optional[str], op_root: Optional[str]) -> List[Tuple[List[str], List[str]]]:
+    """sorted sub-video folders, sorted files inside (test_helper.py:404-411, two_stream_dataset.py:515-518).  One root
+    may be None (a single-stream set): the folders are those of the other root, and the missing kind's lists are empty."""
     out = []
-    for name in sorted(os.listdir(rgb_root)):
-        frames = sorted(glob.glob(os.path.join(rgb_root, name, "*")))
-        flows = sorted(glob.glob(os.path.join(op_root, name, "*")))
+    for name in sorted(os.listdir(rgb_root if rgb_root is not None else op_root)):
+        frames = sorted(glob.glob(os.path.join(rgb_root, name, "*"))) if rgb_root is not None else []
+        flows = sorted(glob.glob(os.path.join(op_root, name, "*"))) if op_root is not None else []
         out.append((frames, flows))
     return out
 
@@ -265,6 +266,34 @@ class ClipSampler:
                             float(st["cached_gaussian"])))
 
 
+class SingleClipSampler:
+    """The draw of one stream trained on its own (stage 1 of the reference's recipe: `clip_Train_DS.__getitem__`,
+    two_stream_dataset.py:287-333, behind `train_single_Helper`): one `np.random.RandomState(seed)` and, per sample,
+    `vid = randint(0, n_videos)`, then `start = randint(0, len(vid) - clip_len)` - the exclusive upper bound kept, as in
+    `ClipSampler`.  `draw(b)` returns (video, start) int arrays; `get_state` / `set_state` as `ClipSampler`'s."""
+
+    def __init__(self, lens: Sequence[int], clip_len: int, seed: int = 2017, what: str = "clip"):
+        self.lens, self.clip_len = [int(n) for n in lens], int(clip_len)
+        if not self.lens:
+            raise ValueError("SingleClipSampler: no sub-videos")
+        short = [i for i, n in enumerate(self.lens) if n <= self.clip_len]
+        if short:
+            raise ValueError(f"SingleClipSampler: {what} sub-videos {short} have <= {self.clip_len} frames: the draw rule "
+                             f"needs at least {self.clip_len + 1}")
+        self.rng = np.random.RandomState(seed)
+
+    def draw(self, batch: int) -> Tuple[np.ndarray, np.ndarray]:
+        out = np.empty((2, batch), np.int64)
+        r = self.rng
+        for i in range(batch):
+            v = r.randint(0, len(self.lens))
+            out[0, i], out[1, i] = v, r.randint(0, self.lens[v] - self.clip_len)
+        return out[0], out[1]
+
+    get_state = ClipSampler.get_state
+    set_state = ClipSampler.set_state
+
+
 def _size_wh(size) -> Tuple[int, int]:
     """`size` as (width, height): an int is a square"""
     if isinstance(size, int):
@@ -294,10 +323,15 @@ class ClipBank:
     are decoded by a pool of `workers` threads (PIL releases the GIL) into pinned staging buffers (two, alternating,
     each guarded by an event so it is not rewritten before its copy ran), copied to the device at their native
     resolution (which may differ between sub-videos) and resized into the sub-video's slice on a side stream.
-    `fill_seconds`: wall time of the whole fill."""
+    `fill_seconds`: wall time of the whole fill.
 
-    def __init__(self, rgb_root: str, op_root: str, size, device, workers: int = 8, budget_gb: Optional[float] = None,
-                 rgb_len: int = 5, op_len: int = 4, bgr: bool = False):
+    One kind (a single-stream training stage): `rgb_root=None` or `op_root=None`.  Such a bank decodes, uploads and
+    budgets only its kind (the other bank is None), `global_index(vid, start)` and `gather(first)` take and return that
+    kind alone, and the gather is one launch of `ammc_gather_clips_one`, bit-identical to the matching half of the
+    two-kind gather.  `kinds`: ("rgb", "op"), ("rgb",) or ("op",)."""
+
+    def __init__(self, rgb_root: Optional[str], op_root: Optional[str], size, device, workers: int = 8,
+                 budget_gb: Optional[float] = None, rgb_len: int = 5, op_len: int = 4, bgr: bool = False):
         import time
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -306,9 +340,12 @@ class ClipBank:
         if (self.width * self.height) % 4:
             raise _lib.AmmcHipError(f"ClipBank: {self.width}x{self.height} frames: the gather needs H * W % 4 == 0")
         self.rgb_len, self.op_len, self.bgr, self.workers = int(rgb_len), int(op_len), bool(bgr), max(1, int(workers))
+        if rgb_root is None and op_root is None:
+            raise ValueError("ClipBank: needs rgb_root, op_root or both")
+        self.kinds = tuple(k for k, root in (("rgb", rgb_root), ("op", op_root)) if root is not None)
         self.videos = list_subvideos(rgb_root, op_root)
         if not self.videos:
-            raise ValueError(f"ClipBank: no sub-video folders under {rgb_root}")
+            raise ValueError(f"ClipBank: no sub-video folders under {rgb_root if rgb_root is not None else op_root}")
         self.rgb_count = np.array([len(f) for f, _ in self.videos], np.int64)
         self.op_count = np.array([len(o) for _, o in self.videos], np.int64)
         self.rgb_start = np.concatenate([[0], np.cumsum(self.rgb_count)[:-1]]).astype(np.int64)
@@ -327,8 +364,11 @@ class ClipBank:
         if max(self.n_rgb, self.n_op) >= 2**31:
             raise _lib.AmmcHipError("ClipBank: more than 2^31 frames (the gather's indices are int32)")
         t0 = time.perf_counter()
-        self.rgb = torch.empty(self.n_rgb, 3, self.height, self.width, dtype=torch.uint8, device=self.device)
-        self.op = torch.empty(max(self.n_op, 1), self.height, self.width, dtype=torch.float32, device=self.device)
+        self.rgb = self.op = None
+        if "rgb" in self.kinds:
+            self.rgb = torch.empty(self.n_rgb, 3, self.height, self.width, dtype=torch.uint8, device=self.device)
+        if "op" in self.kinds:
+            self.op = torch.empty(max(self.n_op, 1), self.height, self.width, dtype=torch.float32, device=self.device)
         self._fill()
         self.fill_seconds = time.perf_counter() - t0
         self._idx_pinned = [torch.empty(0, dtype=torch.int32).pin_memory() for _ in range(2)]
@@ -400,39 +440,63 @@ class ClipBank:
 
     # -- gather --------------------------------------------------------------------------------------------------------
 
-    def global_index(self, rgb_vid, rgb_start, op_vid, op_start) -> Tuple[np.ndarray, np.ndarray]:
-        """(sub-video, start) pairs (`ClipSampler.draw`) -> global first-frame indices of the banks"""
+    def _single(self) -> Optional[str]:
+        return self.kinds[0] if len(self.kinds) == 1 else None
+
+    def global_index(self, *pairs):
+        """(sub-video, start) pairs (`ClipSampler.draw`) -> global first-frame indices of the banks; a one-kind bank takes
+        the (video, start) of `SingleClipSampler.draw` and returns one array"""
+        one = self._single()
+        if one is not None:
+            vid, start = pairs
+            return (self.rgb_start if one == "rgb" else self.op_start)[np.asarray(vid)] + np.asarray(start)
+        rgb_vid, rgb_start, op_vid, op_start = pairs
         return (self.rgb_start[np.asarray(rgb_vid)] + np.asarray(rgb_start),
                 self.op_start[np.asarray(op_vid)] + np.asarray(op_start))
 
     def validate(self, rgb_first, op_first) -> Tuple[np.ndarray, np.ndarray]:
         """host check of every index (`check_clip_indices`); raises AmmcHipError"""
+        if self._single() is not None:
+            raise _lib.AmmcHipError(f"ClipBank: a {self._single()}-only bank has no clips of the other kind")
         rf = check_clip_indices("rgb", rgb_first, self.rgb_start, self.rgb_count, self.rgb_len)
         of = check_clip_indices("op", op_first, self.op_start, self.op_count, self.op_len)
         if rf.size != of.size or rf.size == 0:
             raise _lib.AmmcHipError("ClipBank.gather: need as many (>= 1) rgb as op indices")
         return rf, of
 
-    def gather(self, rgb_first, op_first) -> Tuple[torch.Tensor, torch.Tensor]:
-        """host int arrays of global first frames -> (rgb float32 [B, rgb_len, 3, H, W], op float32 [B, op_len, 2, H, W])
-        on the current stream: the indices go H2D through one of two pinned buffers (event-guarded), then one launch"""
-        rf, of = self.validate(rgb_first, op_first)
-        b = rf.size
+    def _indices_to_device(self, rows) -> torch.Tensor:
+        """validated host index rows -> device int32 [len(rows), B] on the current stream, through one of two pinned
+        buffers (event-guarded)"""
+        n, b = len(rows), rows[0].size
         k = self._idx_turn
         self._idx_turn ^= 1
         if self._idx_events[k] is not None:
             self._idx_events[k].synchronize()                 # the copy that last read this buffer has run
-        if self._idx_pinned[k].numel() < 2 * b:
-            self._idx_pinned[k] = torch.empty(2 * b, dtype=torch.int32).pin_memory()
-        host = self._idx_pinned[k][:2 * b].view(2, b)
+        if self._idx_pinned[k].numel() < n * b:
+            self._idx_pinned[k] = torch.empty(n * b, dtype=torch.int32).pin_memory()
+        host = self._idx_pinned[k][:n * b].view(n, b)
         hn = host.numpy()
-        hn[0], hn[1] = rf, of
+        for i, r in enumerate(rows):
+            hn[i] = r
         stream = torch.cuda.current_stream(self.device)
-        idx = torch.empty(2, b, dtype=torch.int32, device=self.device)
+        idx = torch.empty(n, b, dtype=torch.int32, device=self.device)
         idx.copy_(host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(stream)
         self._idx_events[k] = ev
+        return idx
+
+    def gather(self, *first):
+        """host int arrays of global first frames -> (rgb float32 [B, rgb_len, 3, H, W], op float32 [B, op_len, 2, H, W])
+        on the current stream: the indices go H2D through one of two pinned buffers (event-guarded), then one launch.
+        A one-kind bank: `gather(first)` -> that kind's clips alone (`ammc_gather_clips_one`)."""
+        one = self._single()
+        if one is not None:
+            return self._gather_one(one, *first)
+        rf, of = self.validate(*first)
+        b = rf.size
+        idx = self._indices_to_device((rf, of))
+        stream = torch.cuda.current_stream(self.device)
         rgb = torch.empty(b, self.rgb_len, 3, self.height, self.width, dtype=torch.float32, device=self.device)
         op = torch.empty(b, self.op_len, 2, self.height, self.width, dtype=torch.float32, device=self.device)
         _lib.check(_lib.load().ammc_gather_clips(self.rgb.data_ptr(), self.n_rgb, self.op.data_ptr(), self.n_op,
@@ -440,6 +504,21 @@ class ClipBank:
                                                  self.height, self.width, rgb.data_ptr(), op.data_ptr(), stream.cuda_stream),
                    "gather_clips")
         return rgb, op
+
+    def _gather_one(self, kind: str, first) -> torch.Tensor:
+        rgb = kind == "rgb"
+        starts, counts = (self.rgb_start, self.rgb_count) if rgb else (self.op_start, self.op_count)
+        clip, n, bank = (self.rgb_len, self.n_rgb, self.rgb) if rgb else (self.op_len, self.n_op, self.op)
+        f = check_clip_indices(kind, first, starts, counts, clip)
+        if f.size == 0:
+            raise _lib.AmmcHipError("ClipBank.gather: need >= 1 index")
+        idx = self._indices_to_device((f,))
+        stream = torch.cuda.current_stream(self.device)
+        out = torch.empty(f.size, clip, 3 if rgb else 2, self.height, self.width, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().ammc_gather_clips_one(bank.data_ptr(), n, 0 if rgb else 1, idx[0].data_ptr(), f.size, clip,
+                                                     self.height, self.width, out.data_ptr(), stream.cuda_stream),
+                   "gather_clips_one")
+        return out
 
 
 def check_clip_indices(what: str, first, starts: np.ndarray, counts: np.ndarray, clip: int) -> np.ndarray:

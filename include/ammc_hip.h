@@ -441,6 +441,13 @@ int ammc_flows_resize_c0(const float* src, int32_t n, int32_t h, int32_t w, floa
 int ammc_gather_clips(const uint8_t* rgb_bank, int64_t n_rgb, const float* op_bank, int64_t n_op, const int32_t* rgb_first,
                       const int32_t* op_first, int32_t batch, int32_t rgb_len, int32_t op_len, int32_t h, int32_t w,
                       float* rgb_out, float* op_out, void* stream);
+/* The clips of ONE bank, for a single-stream training stage (pipeline.ClipBank with one root): kind 0 = the rgb bank
+ * (uint8 [n][3][h][w]) -> out float32 [batch][len][3][h][w], kind 1 = the op bank (float32 [n][h][w]) -> out float32
+ * [batch][len][2][h][w]; bit-identical to the rgb / op half of ammc_gather_clips for the same indices.  Same
+ * requirements (the bank 4-byte (rgb) or 16-byte (op) aligned, batch * planes <= 65535 with 3 planes per rgb frame and
+ * one per op frame) and the same NaN output for an index outside [0, n - len]. */
+int ammc_gather_clips_one(const void* bank, int64_t n, int32_t kind, const int32_t* first, int32_t batch, int32_t len,
+                          int32_t h, int32_t w, float* out, void* stream);
 
 /* nn.BatchNorm2d in training mode (unet.py:12,15).  Per-channel reductions write
  * partial[ammc_chan_reduce_blocks(B*H*W)][Q][C]; the finalizers combine them in fp64, fixed order. */
