@@ -27,54 +27,16 @@ from .engine import Act, _cin_pad, _kpad, _ptr, s16_variant
 
 BN_MOMENTUM = 0.1
 CHANS = (64, 128, 256, 512)
-# 3x3 convolutions of the training path (forward and input-gradient): "s16" = the fp32-equivalent split-fp16 kernels
-# of the inference path (operands converted per launch, fp32 outputs; everything else - statistics, weight gradients,
-# 1x1 / transposed convs - stays on the fp32 kernels), "fp32" = exact fp32 MFMA throughout
+# convolutions of the training path: "s16" = the fp32-equivalent split-fp16 kernels of the inference path for the 3x3
+# layers (forward, input and weight gradients) and the ConvTranspose layers (fp32 outputs or S16 twins; statistics and
+# the memory block's 1x1 convs stay on the fp32 kernels), "fp32" = exact fp32 MFMA throughout
 # Process-wide default; per model: `model.train_precision = "fp32" | "s16"` (read when the engine is built / rebuilt)
 TRAIN_PRECISION = os.environ.get("AMMC_TRAIN_PRECISION", "s16")
-WGRAD_S16 = os.environ.get("AMMC_WGRAD_S16", "1") != "0"          # the 3x3 weight gradients as well (wgrad_s16.hip)
-# ConvTranspose forward / input gradient on the S16 kernels too: opt-in - its short-K GEMMs gain less than the operand
-# re-encoding costs (74.9 ms/step without, 75.5 with)
-CONVT_S16 = os.environ.get("AMMC_CONVT_S16", "0") != "0"          # ConvTranspose input gradient too (re-encodes its operand)
-# Round 4: every activation that only split-fp16 kernels read again is written as its S16 twin BY ITS PRODUCER (the
-# BatchNorm apply pass stores the fp32 tensor and the twin in one sweep, the max-pool runs on twins, the ConvTranspose
-# forward runs on conv_gemm_s16 with an S16 output): no fp32 -> S16 re-encoding pass of an activation is left in the
-# forward (they were 2.4 ms of the 70-ms step), and the ConvTranspose forward leaves the fp32 MFMA pipe.
-TWIN_S16 = os.environ.get("AMMC_TWIN_S16", "1") != "0"
-# ... and in the backward the gradient of a ConvTranspose's output is re-encoded ONCE (its max |g| comes out of the
-# bias-gradient pass that reads it anyway, the re-encoding touches its half of the concat buffer only) for BOTH of the
-# layer's gradient kernels: weight gradient on ammc_conv_wgrad_s16 (2x2 window, stride 2), input gradient on
-# ammc_conv_gemm_s16.  (AMMC_CONVT_S16 alone re-encoded the whole concat buffer for the input gradient only: no gain.)
-CONVT_GRADS_S16 = os.environ.get("AMMC_CONVT_GRADS_S16", "1") != "0"
-# all 3x3 filters of a step packed to their S16 images by ONE launch per direction (ammc_pack_filters_s16) instead of a
-# pack and a split launch per layer and direction (~140 launches of 5-8 us per step)
-PACK_BATCH = os.environ.get("AMMC_PACK_BATCH", "1") != "0"
-# BatchNorm batch statistics as a second output of the convolution that produces the tensor (AmmcConvDesc.stats: one
-# partial row per 8 x 32 output patch, from the accumulators) instead of a pass that re-reads it
-FUSE_BN_STATS = os.environ.get("AMMC_FUSE_BN_STATS", "1") != "0"
 STAT_SEG = 128
-# max-pool backward from the window positions recorded by the forward (a byte per pooled element) instead of finding the
-# maxima again from the pooled tensor's S16 twin
-POOL_IDX = os.environ.get("AMMC_POOL_IDX", "1") != "0"
-# ... and the pooled tensor + those positions as extra outputs of the BatchNorm apply pass that writes the tensor
-# (ammc_scale_shift_act_s16_pool_f32) instead of a max-pool pass that reads it back
-FUSE_POOL_APPLY = os.environ.get("AMMC_FUSE_POOL_APPLY", "1") != "0"
-# ... and in the backward the gradient of a pooled tensor (skip gradient + max-pool backward) is never materialised: the
-# BatchNorm-backward passes of the unit that produced the tensor form it on the fly from those positions
-FUSE_UNPOOL_BN = os.environ.get("AMMC_FUSE_UNPOOL_BN", "1") != "0"
-# the reduction of a unit's BatchNorm backward (sum g, sum g xhat, max |g|, max |xhat|) as a second output of the
-# input-gradient convolution that PRODUCES the unit's output gradient (AmmcConvDesc.bn_c), instead of a pass that reads
-# the gradient back
-FUSE_BN_BWD_STATS = os.environ.get("AMMC_FUSE_BN_BWD_STATS", "1") != "0"
 # one rank: the rgb and the flow stream of the network (independent between the bridge / memory joints) are issued on two
 # HIP streams, so that one's HBM-bound BatchNorm passes (~1170 W at 6 TB/s) run beside the other's MFMA-bound convolutions
 # instead of after them: the step is energy-bound and those passes leave ~230 W of the 1400 W cap unused
 TWO_STREAMS = os.environ.get("AMMC_TWO_STREAMS", "1") != "0"
-# the 3x3 weight gradients' split partials as slabs summed straight into the parameter gradient (round 5) instead of fp32
-# atomics into a zeroed packed buffer + an unpack launch
-WGRAD_SLABS = os.environ.get("AMMC_WGRAD_SLABS", "1") != "0"
-MID_S16 = os.environ.get("AMMC_MID_S16", "1") != "0"              # double_conv middle activations exist as S16 only
-FUSE_BN_BWD = os.environ.get("AMMC_FUSE_BN_BWD", "1") != "0"      # BN backward writes the S16 twin of dc (one rank)
 
 
 class _WS:
@@ -147,7 +109,6 @@ class _Ops:
         self.sync_force = False         # parallel.sync_statistics(..., force=True): the collective path with one rank too
         self.s16 = (precision or TRAIN_PRECISION) == "s16"
         self._shadows: Dict[int, torch.Tensor] = {}
-        self.amax = ws.buf(256, dtype=torch.int32)         # slots of ammc_absmax_bits_f32 / bn_bwd_apply
         self.side = None                                   # two HIP streams of `_side_by_side`, made on first use
         self._wgrad_slabs: Dict[int, torch.Tensor] = {}    # slab workspace of the 3x3 weight gradients, per HIP stream
         # bench.py: a list here brackets every MFMA launch of the 3x3 layers with HIP events on the launch stream and
@@ -203,26 +164,15 @@ class _Ops:
         t.rs, t.bs = a.rs, a.bs                       # (a cropped view keeps its buffer's strides)
         return t
 
-    def to_s16(self, x: Act, rescale: bool = False, have_amax: bool = False, amax: Optional[torch.Tensor] = None):
-        """re-encode the fp32 buffer behind `x` into its S16 twin; `rescale` (gradients): first bring it into the half
-        range by a power of two found on the device (`have_amax`: the producer already left max |x| in the slots;
-        `amax`: the caller's own slots, zero at the start of the backward pass - else the shared ones, cleared here).
-        Returns (twin, inverse scale [1] or None)."""
+    def to_s16(self, x: Act, amax: Optional[torch.Tensor] = None, have_amax: bool = False):
+        """re-encode the fp32 buffer behind `x` into its S16 twin; `amax` (gradients): first bring it into the half range
+        by a power of two found on the device, through the caller's own max |x| slots (zero at the start of the backward
+        pass; `have_amax`: the producer already left max |x| in them).  Returns (twin, inverse scale [1] or None)."""
         lib, s = self.lib, self.s
         xs = self.shadow(x)
         inv = None
-        if rescale:
+        if amax is not None:
             inv = torch.empty(1024, device=self.dev, dtype=torch.float32)
-            if amax is None:
-                # the SHARED slots: one user at a time.  Inside `_side_by_side` two generators run on two HIP streams at
-                # once and each must bring its own slots (the units do: per-unit amax buffers) - a caller that forgot
-                # would race silently, so it is refused here
-                if self.side is not None and torch.cuda.current_stream(self.dev) in self.side:
-                    raise RuntimeError("to_s16(rescale=True) without its own `amax` slots on a side stream of "
-                                       "_side_by_side: the shared slots would be raced by the other stream")
-                amax = self.amax
-                if not have_amax:
-                    amax.zero_()
             if not have_amax:
                 _chk(lib.ammc_absmax_bits_f32(_ptr(x.buf), x.buf.numel(), amax.data_ptr(), s), "absmax")
             _chk(lib.ammc_split_rows_scaled_f32(_ptr(x.buf), x.buf.numel(), _ptr(xs.buf), amax.data_ptr(), _ptr(inv),
@@ -235,9 +185,10 @@ class _Ops:
                   out_oihw: Optional[torch.Tensor] = None):
         """weight gradient from the S16 twins of the output gradient and of the layer input (3x3; ntaps 4 / a_step 2: the
         ConvTranspose form of ammc_conv_wgrad_f32 - g = the layer input, a = the output gradient at twice the resolution).
-        `out_oihw` (3x3 layers): the parameter's gradient tensor; where the layer's kernel has a slab form (round 5,
-        AMMC_WGRAD_SLABS) the split partials are stored as slabs and summed straight into it - no atomics into the zeroed
-        packed buffer `dw`, no unpack launch - and the call returns True (the caller then skips its unpack)."""
+        `out_oihw` (3x3 layers): the parameter's gradient tensor; where the layer's kernel has a slab form the split
+        partials are stored as slabs and summed straight into it - no atomics into the zeroed packed buffer `dw`, no
+        unpack launch - and the call returns True (the caller then skips its unpack).  Kernels without a slab form
+        (`ammc_conv_wgrad_s16_slab_floats` == 0) and the ConvTranspose form take the atomics."""
         d = AmmcWgradDesc()
         d.g, d.a, d.dw, d.zeros = g16.pix0(), (a16.tap0() if ntaps == 9 else a16.pix0()), _ptr(dw), _ptr(self.zeros)
         d.batch, d.height, d.width = g16.B, g16.H, g16.W
@@ -247,7 +198,7 @@ class _Ops:
         label = ("conv_wgrad_s16 (3x3 weight gradients: wgrad_tap3_s16 / wgrad_tap_s16 instances)" if ntaps == 9 else
                  "conv_wgrad_s16 (ConvTranspose weight gradients: wgrad_s16)")
         flops = 2.0 * g16.B * g16.H * g16.W * ntaps * (true_nc if true_nc is not None else n * cin)      # unpadded channels
-        if out_oihw is not None and ntaps == 9 and a_step == 1 and WGRAD_SLABS:
+        if out_oihw is not None and ntaps == 9 and a_step == 1:
             need = int(self.lib.ammc_conv_wgrad_s16_slab_floats(C.byref(d)))
             if need > 0:
                 # one slab workspace per HIP stream (the rgb / flow halves of a step run on two): sized for the largest user
@@ -266,13 +217,14 @@ class _Ops:
         return False
 
     def conv_s16(self, x: Act, w: torch.Tensor, y: Act, *, ntaps, cin, n, res: Optional[Act] = None, what="conv",
-                 rescale: bool = False, pre=None, shift=None, up=1, cgroup=None, x_step=1, y_s16: bool = False,
+                 pre=None, shift=None, up=1, cgroup=None, x_step=1, y_s16: bool = False,
                  w16: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, bn=None):
         """3x3 conv on the split-fp16 MFMA kernels: x (fp32, any channel slice of its buffer) is re-encoded into its S16
-        twin (or `pre` = what `to_s16` returned for it), the packed filter likewise; fp32 output (+ fp32 residual), or -
-        `y_s16`: y is the S16 twin itself - an S16 output.  ammc_conv_gemm_s16 picks the kernel."""
+        twin (or `pre` = what `to_s16` returned for it), the packed filter likewise (`w16=None`: per layer - `BlockEngine`,
+        which never runs the batched pack, and the ConvTranspose layers); fp32 output (+ fp32 residual), or - `y_s16`: y is
+        the S16 twin itself - an S16 output.  ammc_conv_gemm_s16 picks the kernel."""
         lib, s = self.lib, self.s
-        xs, inv = pre if pre is not None else self.to_s16(x, rescale)
+        xs, inv = pre if pre is not None else self.to_s16(x)
         if w16 is None:                              # (else: the S16 image is already there - the step's batched pack)
             w16 = torch.empty_like(w)
             _chk(lib.ammc_split_rows_f32(_ptr(w), w.numel(), _ptr(w16), s), "split_rows(w)")
@@ -455,6 +407,7 @@ class _ConvBN:
         self.cout, self.cin = conv.weight.shape[0], conv.weight.shape[1]
         self.cin_p = _cin_pad(self.cin)
         assert x.c == self.cin_p or x.c == self.cin, (name, x.c, self.cin_p)
+        self.s16 = ops.s16 and self.cin_p >= 8         # this layer's forward and gradients run on the split-fp16 kernels
         self.kpad = _kpad(9 * self.cin_p)
         self.wp = ws.buf(self.cout, self.kpad)                       # forward filter, packed
         self.craw = ws.act(x.B, x.H, x.W, self.cout)                 # raw conv output (saved for backward)
@@ -462,9 +415,9 @@ class _ConvBN:
         self.scale, self.shift = ws.buf(self.cout), ws.buf(self.cout)
         self.nblk = ops.lib.ammc_chan_reduce_blocks(x.B * x.H * x.W)
         self.partial = ws.buf(self.nblk, 4, self.cout)               # Q = 2 sums (+ 2 maxima in the fused S16 backward)
-        # forward statistics from the convolution's own epilogue where its kernel has one (FUSE_BN_STATS)
-        self.stat_rows = (ops.conv_s16_stats_rows(x, self.wp, self.craw, cin=self.cin_p, n=self.cout)
-                          if ops.s16 and self.cin_p >= 8 and FUSE_BN_STATS else 0)
+        # forward statistics from the convolution's own epilogue where its kernel has one, instead of a pass that re-reads
+        # its output; 0 rows (fp32, cin_p < 8, a kernel without that epilogue): the `ammc_bn_stats_f32` pass
+        self.stat_rows = ops.conv_s16_stats_rows(x, self.wp, self.craw, cin=self.cin_p, n=self.cout) if self.s16 else 0
         self.stat_partial = ws.buf(self.stat_rows, 2, self.cout) if self.stat_rows else None
         # thousands of rows (8192 at batch 32, 256x256) are first combined in runs of STAT_SEG by many workgroups
         self.stat_seg = ws.buf((self.stat_rows + STAT_SEG - 1) // STAT_SEG, 2, self.cout) if self.stat_rows > 1024 else None
@@ -475,8 +428,9 @@ class _ConvBN:
         self.rows = max(64, (self.cin + 63) // 64 * 64) if self.cin >= 32 else 0   # dgrad filter rows
         self.wdp = ws.buf(self.rows, _kpad(9 * self.cout)) if self.rows else None
         self.w16 = self.wd16 = None
-        if ops.s16 and self.cin_p >= 8 and PACK_BATCH:
-            # S16 images of the forward / input-gradient filters, written by the step's batched pack (TrainEngine)
+        if self.s16:
+            # S16 images of the forward / input-gradient filters, written by the step's batched pack (TrainEngine): one
+            # launch per direction instead of a pack and a split launch per layer and direction
             self.w16 = ws.buf(self.cout, self.kpad)
             ops.pack_items["fwd"].append((conv.weight, self.w16, self.cout, self.cin, self.cin_p, self.kpad, 0, self.cout))
             if self.rows:
@@ -494,7 +448,7 @@ class _ConvBN:
         batched = self.w16 is not None and o.packed["fwd"]
         if not batched:
             _chk(lib.ammc_pack_conv_weight_f32(_ptr(w), self.cout, self.cin, 3, self.cin_p, _ptr(self.wp), s), "pack")
-        if o.s16 and self.cin_p >= 8:
+        if self.s16:
             o.conv_s16(self.x, self.wp, self.craw, ntaps=9, cin=self.cin_p, n=self.cout, what=self.name,
                        pre=(o.shadow(self.x), None) if self.x_is_s16 else None, w16=self.w16 if batched else None,
                        stats=self.stat_partial)
@@ -555,8 +509,7 @@ class _ConvBN:
         """can this unit's backward take its output gradient as `dy + max-pool backward` formed on the fly (`backward_gen`'s
         `unpool`)?  The one-rank split-fp16 path with the row form of the apply kernel; the caller materialises otherwise."""
         o = self.ops
-        s16_wgrad = o.s16 and self.cin_p >= 8 and WGRAD_S16
-        return bool(FUSE_UNPOOL_BN and FUSE_BN_BWD and o.s16 and s16_wgrad and not o.sync_on and
+        return bool(self.s16 and not o.sync_on and
                     o.lib.ammc_bn_bwd_unpool_supported(self.cout, self.craw.ps, dy.ps, self.dc.ps, self.craw.W))
 
     def dgrad_stats_for(self, producer: "_ConvBN", dy: Act):
@@ -566,8 +519,7 @@ class _ConvBN:
         o = self.ops
         key = id(producer)
         if key not in self._bwd_stats:
-            ok = (FUSE_BN_BWD_STATS and FUSE_BN_BWD and o.s16 and self.cin_p >= 8 and WGRAD_S16 and producer.rows == self.cout
-                  and producer.wdp is not None)
+            ok = self.s16 and producer.rows == self.cout and producer.wdp is not None
             rows = o.conv_s16_stats_rows(producer.dc, producer.wdp, dy, cin=producer.cout, n=producer.rows, bn=self) if ok else 0
             if rows:
                 part = o.ws.buf(rows, 4, self.cout)
@@ -588,8 +540,7 @@ class _ConvBN:
         o, lib, s = self.ops, self.ops.lib, self.ops.s
         c = self.craw
         world = o.sync_world
-        s16_wgrad = o.s16 and self.cin_p >= 8 and WGRAD_S16
-        fused_amax = o.s16 and (da is not None or s16_wgrad)
+        fused_amax = o.s16 and (da is not None or self.s16)
         if unpool is not None:
             assert self.unpool_fusable(dy)
             dpo, idx = unpool
@@ -609,7 +560,7 @@ class _ConvBN:
                                                       dc16.pix0(), None, *self.dc.strides, c.B, c.H, c.W, self.cout,
                                                       self.amax.data_ptr(), _ptr(inv), 1024, s), "bn_bwd_apply_s16(unpool)")
             pre = (dc16, inv)
-        elif fused_amax and not o.sync_on and FUSE_BN_BWD:
+        elif fused_amax and not o.sync_on:
             # one rank, S16 consumers: the reduction also bounds max |dc|, so the apply pass writes the S16 twin of dc
             # directly (fp32 dc only where the fp32 weight-gradient kernel still reads it)
             part, nblk = self.partial, self.nblk
@@ -632,11 +583,13 @@ class _ConvBN:
             inv = torch.empty(1024, device=o.dev, dtype=torch.float32)
             _chk(lib.ammc_bn_bwd_apply_s16_f32(c.pix0(), *c.strides, dy.pix0(), *dy.strides, _ptr(self.mean),
                                                _ptr(self.invstd), _ptr(self.scale), _ptr(self.shift), _ptr(sums), 1,
-                                               dc16.pix0(), None if s16_wgrad else self.dc.pix0(), *self.dc.strides,
+                                               dc16.pix0(), None if self.s16 else self.dc.pix0(), *self.dc.strides,
                                                c.B, c.H, c.W, self.cout, self.amax.data_ptr(), _ptr(inv), 1024, s),
                  "bn_bwd_apply_s16")
             pre = (dc16, inv)
         else:
+            # fp32, and the S16 path with synchronised statistics (DDP, `sync_statistics(force=True)`): an fp32 dc, which
+            # the S16 consumers get re-encoded below
             _chk(lib.ammc_bn_bwd_reduce_f32(c.pix0(), *c.strides, dy.pix0(), *dy.strides, _ptr(self.mean), _ptr(self.invstd),
                                             _ptr(self.scale), _ptr(self.shift), 1, c.B, c.H, c.W, self.cout,
                                             _ptr(self.partial), s), "bn_bwd_reduce")
@@ -656,10 +609,10 @@ class _ConvBN:
                                            _ptr(self.scale), _ptr(self.shift), _ptr(sums), 1, self.dc.pix0(),
                                            *self.dc.strides, c.B, c.H, c.W, self.cout,
                                            self.amax.data_ptr() if fused_amax else None, s), "bn_bwd_apply")
-            pre = o.to_s16(self.dc, rescale=True, have_amax=True, amax=self.amax) if fused_amax else None   # shared by wgrad and dgrad
+            pre = o.to_s16(self.dc, amax=self.amax, have_amax=True) if fused_amax else None   # shared by wgrad and dgrad
         dw = torch.empty_like(self.conv.weight)
         summed = False
-        if pre is not None and self.cin_p >= 8 and WGRAD_S16:
+        if self.s16:
             summed = o.wgrad_s16(pre[0], o.shadow(self.x), self.dwp, pre[1], n=self.cout, cin=self.cin_p,
                                  what=self.name + ".wgrad", true_nc=self.cout * self.cin, out_oihw=dw)   # shadow(x): the twin the forward conv left behind
         else:
@@ -674,9 +627,9 @@ class _ConvBN:
                 _chk(lib.ammc_pack_conv_dgrad_weight_f32(_ptr(w), self.cout, self.cin, self.cout, self.rows,
                                                          _ptr(self.wdp), s), "pack_dgrad")
             if o.s16:
-                st = consumer.dgrad_stats_for(self, da) if (consumer is not None and da_res is None and pre is not None) else None
+                st = consumer.dgrad_stats_for(self, da) if (consumer is not None and da_res is None) else None
                 o.conv_s16(self.dc, self.wdp, da, ntaps=9, cin=self.cout, n=self.rows, res=da_res,
-                           what=self.name + ".dgrad", rescale=True, pre=pre, w16=self.wd16 if batched else None,
+                           what=self.name + ".dgrad", pre=pre, w16=self.wd16 if batched else None,
                            stats=st[1] if st else None, bn=consumer if st else None)
             else:
                 o.conv(self.dc, self.wdp, da, ntaps=9, cin=self.cout, n=self.rows, res=da_res, what=self.name + ".dgrad")
@@ -688,8 +641,9 @@ class _DoubleConv:
         self.mid = ops.ws.act(x.B, x.H, x.W, seq[0].weight.shape[0])
         self.u0 = _ConvBN(ops, seq[0], seq[1], x, self.mid, None, name + ".conv0")
         self.u1 = _ConvBN(ops, seq[3], seq[4], self.mid, y, res, name + ".conv1")
-        if ops.s16 and WGRAD_S16 and MID_S16 and self.u1.cin_p >= 8:
-            # `mid` is read by conv1 (forward) and by conv1's weight gradient only, both on the S16 kernels
+        if self.u1.s16:
+            # `mid` is read by conv1 (forward) and by conv1's weight gradient only, both on the S16 kernels: it exists as
+            # its S16 twin only
             self.u0.y_s16_only = self.u1.x_is_s16 = True
         self.dmid = ops.ws.act(x.B, x.H, x.W, seq[0].weight.shape[0])
 
@@ -789,40 +743,41 @@ class _Stream:
         self.outc_amax = ws.zbuf(256, dtype=torch.int32)
         self.outc_wdp = ws.buf(64, _kpad(9 * 64))
         self.scratch = ws.buf(lib.ammc_chan_reduce_blocks(B * H * W) * 512 + 1024)
-        # S16 twins written by their producers (TWIN_S16): skips and decoder outputs by the BatchNorm apply pass, pooled
-        # tensors by the S16 max-pool, the up half of the concat buffers by the ConvTranspose on conv_gemm_s16
-        self.twins = bool(ops.s16 and WGRAD_S16 and TWIN_S16)
-        self.pool_idx = None          # per level: window positions of the pooled maxima (a byte each; twins)
+        # S16 twins written by their producers: skips and decoder outputs by the BatchNorm apply pass (the fp32 tensor and
+        # the twin in one sweep), pooled tensors by the S16 max-pool, the up half of the concat buffers by the
+        # ConvTranspose on conv_gemm_s16 - no pass re-encodes an activation that only split-fp16 kernels read again
+        self.twins = ops.s16
+        # per level: window positions of the pooled maxima (a byte each; twins), which the max-pool backward routes by
+        # instead of finding the maxima again
+        self.pool_idx = None
         self.pool_fused = [False] * 3  # per level: pooled twin + positions come out of the skip block's apply pass
         self.bottom_twin = False                    # the decoder input's twin is written by ITS producer (set by the owner)
         if self.twins:
             for blk in (self.inc, self.down[0], self.down[1]):
                 blk.emit_twin()                     # skip[0..2]: read by the pool and by the decoder's first conv
-                # ... as twins; the max-pool backward finds its arg-max on the twin as well (the values the forward's
-                # pool compared), so the fp32 skip tensor has no reader and is not written
+                # ... as twins; the max-pool backward routes by the positions the forward's pool recorded, so the fp32
+                # skip tensor has no reader and is not written
                 blk.u1.y_s16_only = True
             for blk in self.down + self.up_dc:
                 blk.input_has_twin()                # pooled[i] / cat[lvl]
             for blk in self.up_dc:
                 blk.emit_twin()                     # read by the next ConvTranspose / the output layer
-                if CONVT_GRADS_S16:
-                    # ... and by nothing else: the next ConvTranspose's forward AND weight gradient, the output layer and
-                    # its weight gradient all read the twin - the fp32 tensor would be written for nobody
-                    blk.u1.y_s16_only = True
+                # ... and by nothing else: the next ConvTranspose's forward AND weight gradient, the output layer and its
+                # weight gradient all read the twin - the fp32 tensor would be written for nobody
+                blk.u1.y_s16_only = True
             if not has_vq:
                 self.down[2].emit_twin()            # x4 is the decoder's input
                 self.bottom_twin = True
-            if POOL_IDX:
-                self.pool_idx = [torch.empty(q.B, q.H, q.W, q.c, dtype=torch.uint8, device=ops.dev) for q in self.pooled]
-                for i, blk in enumerate((self.inc, self.down[0], self.down[1])):
-                    sk, c8 = self.skip[i], CHANS[i] >> 3
-                    # (the kernel's own verdict - row form available, strides in range, AMMC_ROW_KERNELS - not a copy of its
-                    # conditions: a geometry it refuses keeps the two separate passes instead of raising in the forward)
-                    p16 = ops.shadow(self.pooled[i])
-                    if FUSE_POOL_APPLY and lib.ammc_scale_shift_act_s16_pool_supported(
-                            CHANS[i], sk.H, sk.W, blk.u1.craw.rs, blk.u1.craw.ps, sk.rs, sk.ps, p16.ps):
-                        blk.u1.pool_out = (p16, self.pool_idx[i])
-                        self.pool_fused[i] = True
+            self.pool_idx = [torch.empty(q.B, q.H, q.W, q.c, dtype=torch.uint8, device=ops.dev) for q in self.pooled]
+            for i, blk in enumerate((self.inc, self.down[0], self.down[1])):
+                sk = self.skip[i]
+                # (the kernel's own verdict - row form available, strides in range, AMMC_ROW_KERNELS - not a copy of its
+                # conditions: a geometry it refuses keeps the two separate passes instead of raising in the forward)
+                p16 = ops.shadow(self.pooled[i])
+                if lib.ammc_scale_shift_act_s16_pool_supported(
+                        CHANS[i], sk.H, sk.W, blk.u1.craw.rs, blk.u1.craw.ps, sk.rs, sk.ps, p16.ps):
+                    blk.u1.pool_out = (p16, self.pool_idx[i])
+                    self.pool_fused[i] = True
 
     # ---- forward pieces -------------------------------------------------------------
     def encode_gen(self, x: torch.Tensor):
@@ -835,12 +790,10 @@ class _Stream:
             if self.pool_fused[i]:
                 pass                                # written by inc / down[i - 1]'s apply pass
             elif self.twins:                        # twin -> twin: the fp32 pooled tensor has no reader left
+                # (a pass of its own where `ammc_scale_shift_act_s16_pool_supported` refuses the skip block's geometry)
                 p16, sk16 = o.shadow(p), o.shadow(sk)
-                if POOL_IDX:
-                    _chk(lib.ammc_maxpool2x2_s16_idx(sk16.pix0(), *sk16.strides, p16.pix0(), *p16.strides,
-                                                     self.pool_idx[i].data_ptr(), p.B, p.H, p.W, p.c, s), "pool_s16")
-                else:
-                    _chk(lib.ammc_maxpool2x2_s16(sk16.pix0(), *sk16.strides, p16.pix0(), *p16.strides, p.B, p.H, p.W, p.c, s), "pool_s16")
+                _chk(lib.ammc_maxpool2x2_s16_idx(sk16.pix0(), *sk16.strides, p16.pix0(), *p16.strides,
+                                                 self.pool_idx[i].data_ptr(), p.B, p.H, p.W, p.c, s), "pool_s16")
             else:
                 _chk(lib.ammc_maxpool2x2_f32(sk.pix0(), *sk.strides, p.pix0(), *p.strides, p.B, p.H, p.W, p.c, s), "pool")
             yield from self.down[i].forward_gen()
@@ -897,8 +850,8 @@ class _Stream:
                 o.conv_s16(y, self.up_wp[j], o.shadow(dst), ntaps=1, cin=2 * c, n=4 * c, shift=self.up_b4[j], up=2, cgroup=c,
                            what=f"up{j + 1}.up", pre=(o.shadow(y), None) if has else None, y_s16=True)
             else:
-                (o.conv_s16 if o.s16 and CONVT_S16 else o.conv)(y, self.up_wp[j], dst, ntaps=1, cin=2 * c,
-                                                              n=4 * c, shift=self.up_b4[j], up=2, cgroup=c, what=f"up{j + 1}.up")
+                o.conv(y, self.up_wp[j], dst, ntaps=1, cin=2 * c, n=4 * c, shift=self.up_b4[j], up=2, cgroup=c,
+                       what=f"up{j + 1}.up")
             yield from self.up_dc[j].forward_gen()
             y = self.up_out[j]
         net = self.net
@@ -913,7 +866,7 @@ class _Stream:
         d.cin, d.ntaps, d.n, d.up, d.cgroup, d.act, d.n_store = 64, 9, 32, 1, 32, ACT_TANH, self.cout
         d.y_bs, d.y_rs, d.y_ps, d.y_cs = self.cout * self.H * self.W, self.W, 1, self.H * self.W
         if o.s16:
-            u16 = o.shadow(u3) if self.twins else o.to_s16(u3)[0]       # also the A operand of the weight gradient later
+            u16 = o.shadow(u3)                      # written by up3's apply pass; also the A operand of the weight gradient
             w16 = torch.empty_like(self.outc_wp)
             _chk(lib.ammc_split_rows_f32(_ptr(self.outc_wp), self.outc_wp.numel(), _ptr(w16), s), "split_rows(w)")
             d.x, d.w, d.y_f32 = u16.tap0(), _ptr(w16), 1
@@ -936,8 +889,8 @@ class _Stream:
         grads[net.outc.bias] = o.chan_sum(dp, 32, self.scratch)[:self.cout]
         dw = torch.empty_like(net.outc.weight)
         summed = False
-        if o.s16 and WGRAD_S16:
-            pre = o.to_s16(dp, rescale=True, amax=self.outc_amax)
+        if o.s16:
+            pre = o.to_s16(dp, amax=self.outc_amax)
             summed = o.wgrad_s16(pre[0], o.shadow(self.u3), self.outc_dwp, pre[1], n=32, cin=64, what="outc.wgrad",
                                  true_nc=self.cout * 64, out_oihw=dw)
         else:
@@ -949,7 +902,7 @@ class _Stream:
         _chk(lib.ammc_pack_conv_dgrad_weight_f32(_ptr(net.outc.weight.detach()), self.cout, 64, 32, 64,
                                                  _ptr(self.outc_wdp), s), "pack_dgrad")
         if o.s16:
-            o.conv_s16(dp, self.outc_wdp, self.du[2], ntaps=9, cin=32, n=64, what="outc.dgrad", rescale=True, pre=pre)
+            o.conv_s16(dp, self.outc_wdp, self.du[2], ntaps=9, cin=32, n=64, what="outc.dgrad", pre=pre)
         else:
             o.conv(dp, self.outc_wdp, self.du[2], ntaps=9, cin=32, n=64, what="outc.dgrad")
         for j in (2, 1, 0):
@@ -961,7 +914,8 @@ class _Stream:
             # gradient of the ConvTranspose output: the top-left 2h x 2w of the skip-sized tensor (`up.forward` pads an
             # odd level on the right / bottom, models/unet_parts.py; the pad's gradient is dropped)
             dys = self.dcat[lvl].slice(c, c).crop(2 * x_in.H, 2 * x_in.W)
-            both16 = self.twins and CONVT_GRADS_S16 and (self.bottom_twin if j == 0 else True)
+            # (fp32 gradients: the fp32 path, and `unetmem`'s first level - its input x4q has no twin)
+            both16 = self.twins and (self.bottom_twin if j == 0 else True)
             pre = None
             if both16:
                 # one pass: bias gradient + max |g| of the slice; one strided re-encoding; both gradient kernels read it
@@ -989,9 +943,6 @@ class _Stream:
             dst = self.dbottom if j == 0 else self.du[j - 1]
             if both16:
                 o.conv_s16(dys, self.up_wT[j], dst, ntaps=4, cin=c, n=2 * c, x_step=2, what=f"up{j + 1}.up.dgrad", pre=pre)
-            elif o.s16 and CONVT_S16:
-                o.conv_s16(dys, self.up_wT[j], dst, ntaps=4, cin=c, n=2 * c, x_step=2, rescale=True,
-                           what=f"up{j + 1}.up.dgrad")
             else:
                 o.conv(dys, self.up_wT[j], dst, ntaps=4, cin=c, n=2 * c, x_step=2, what=f"up{j + 1}.up.dgrad")
 
@@ -1025,20 +976,15 @@ class _Stream:
             yield from self.down[i].backward_gen(dy, self.dpooled[i], None, grads, unpool=unpool)
             sk, dpo, add, out = self.skip[i], self.dpooled[i], self.dcat[i].slice(0, CHANS[i]), self.dskip_tot[i]
             unpool = None
-            if self.twins and POOL_IDX and blocks[i].u1.unpool_fusable(add):
+            if self.twins and blocks[i].u1.unpool_fusable(add):
                 # the gradient of skip[i] (skip path + max-pool backward) is formed inside the BatchNorm-backward passes of
                 # the block that produced skip[i]: no pass writes it, none reads it back
                 dy, unpool = add, (dpo, self.pool_idx[i])
                 continue
-            if self.twins and POOL_IDX:
+            if self.twins:                          # (`unpool_fusable` false: synchronised statistics, or the kernel refuses)
                 _chk(lib.ammc_maxpool2x2_bwd_idx_f32(self.pool_idx[i].data_ptr(), dpo.pix0(), *dpo.strides, add.pix0(),
                                                      *add.strides, out.pix0(), *out.strides, dpo.B, dpo.H, dpo.W, sk.H, sk.W,
                                                      dpo.c, s), "maxpool_bwd(idx)")
-            elif self.twins:
-                sk16 = o.shadow(sk)
-                _chk(lib.ammc_maxpool2x2_bwd_s16x_f32(sk16.pix0(), *sk16.strides, dpo.pix0(), *dpo.strides, add.pix0(),
-                                                      *add.strides, out.pix0(), *out.strides, dpo.B, dpo.H, dpo.W, sk.H, sk.W,
-                                                      dpo.c, s), "maxpool_bwd(s16)")
             else:
                 _chk(lib.ammc_maxpool2x2_bwd_f32(sk.pix0(), *sk.strides, dpo.pix0(), *dpo.strides, add.pix0(), *add.strides,
                                                  out.pix0(), *out.strides, dpo.B, dpo.H, dpo.W, sk.H, sk.W, dpo.c, s), "maxpool_bwd")
@@ -1075,8 +1021,8 @@ class TrainEngine:
                     o2f.emit_twin()                 # xb / yb feed the first ConvTranspose of their stream
                     f2o.emit_twin()
                     r.bottom_twin = o.bottom_twin = True
-                    if CONVT_GRADS_S16:             # (forward and weight gradient of that ConvTranspose: twin readers both)
-                        o2f.u1.y_s16_only = f2o.u1.y_s16_only = True
+                    # (forward and weight gradient of that ConvTranspose: twin readers both)
+                    o2f.u1.y_s16_only = f2o.u1.y_s16_only = True
                 st = dict(ops=ops, streams=[r, o], o2f=o2f, f2o=f2o, xb=xb, yb=yb,
                           dzx=ws.act(B, h, w, 512), dzy=ws.act(B, h, w, 512))
             else:
@@ -1107,7 +1053,7 @@ class TrainEngine:
         ops = st["ops"]
         ops.nbt = []
         ops.packed["fwd"] = ops.packed["bwd"] = False
-        if ops.s16 and PACK_BATCH:
+        if ops.s16:
             ops.run_pack("fwd")                    # every 3x3 forward filter of the step -> S16, one launch
         def both(*gens, grads=None):
             if not _side_by_side(ops, grads, *gens):
@@ -1146,7 +1092,7 @@ class TrainEngine:
         streams: List[_Stream] = st["streams"]
         grads: Dict = {}
         st["ops"].ws.zero_step()            # weight-gradient accumulators and max-|g| slots: one memset per 64-MB chunk
-        if st["ops"].s16 and PACK_BATCH:
+        if st["ops"].s16:
             st["ops"].run_pack("bwd")           # every input-gradient filter -> S16, one launch
         reducer = getattr(self.module, "_grad_reducer", None)     # parallel.BucketedGradReducer or None
         sent = set()

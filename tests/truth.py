@@ -69,7 +69,7 @@ def dense(g: torch.Tensor, n: int = DENSE) -> torch.Tensor:
 
 def hip_lookups(net) -> dict:
     """The branch the HIP training forward just took: the memory lookups {"rgb": int64 [N, k], "op": ...} and - where the
-    engine records them (the default split-fp16 training path: one byte per pooled element, `AMMC_POOL_IDX`) - the routes
+    engine records them (the split-fp16 training path: one byte per pooled element, `_Stream.pool_idx`) - the routes
     of its max-pools, "pool": {"rgb.down1": int64 [B, C, h, w] in 0..3, ...} (oracle.maxpool2x2_forced)."""
     st = net._train_engine._last
     out = {p: st["streams"][si].idx.reshape(-1, 2).long().clone() for si, p in enumerate(("rgb", "op"))}
