@@ -120,13 +120,16 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(ConvArgs a) {
   issue_chunk<AJ, BJ>(d, a.cin_log2, sl, (c), a_src, b_src, As + (stage) * A_STAGE + wave * 256, \
                       Bs + (stage) * B_STAGE + wave * 256)
 
-  f32x16 acc[TM][TN];
+  // Two accumulator sets: the MFMAs of a pair of K chunks (64 k-values) chain into `part`, which is then added to `acc`
+  // and cleared.  One chain over the whole of K loses u sqrt(K / 2) of the result to rounding (2.5e-6 of max|y| at
+  // K = 4608, 8x what a blocked sum loses); chains of 64 and K / 64 lose u sqrt(32 + K / 128).
+  f32x16 acc[TM][TN], part[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; part[i][j][r] = 0.f; }
 
   // fragment read addresses (floats): row * 32 + ((2kk + h) ^ swz) * 4
   const int swz = (l31 >> 1) & 7;
@@ -156,7 +159,15 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(ConvArgs a) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][t], bf[j][t], acc[i][j], 0, 0, 0);
+            part[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][t], bf[j][t], part[i][j], 0, 0, 0);
+    }
+    if ((c & 1) || c + 1 == a.nchunks) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { acc[i][j][r] += part[i][j][r]; part[i][j][r] = 0.f; }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
