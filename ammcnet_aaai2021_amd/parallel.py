@@ -19,11 +19,14 @@ choices for BASELINE.json's multi-GPU configs:
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, torch.device]:
@@ -83,16 +86,25 @@ class BucketedGradReducer:
     all-reduced asynchronously as soon as it is full.  `finish()` flushes the tail, waits and
     scatters the averaged values back IN PLACE into the pushed tensors.  `force`: take the collective path with ONE
     rank too (an initialised process group is then required) - the one-GPU proof that the communicator, the
-    asynchronous all-reduce and its ordering against the raw-pointer kernels on torch's current stream work."""
+    asynchronous all-reduce and its ordering against the raw-pointer kernels on torch's current stream work.
 
-    def __init__(self, bucket_mb: float = 25.0, group=None, force: bool = False):
+    Buckets of contiguous fp32 GPU tensors are gathered by `ammc_bucket_pack_f32` and come back through
+    `ammc_bucket_unpack_scale_f32` (csrc/bucket.hip: one launch per 128 members, the 1 / world multiply folded into the
+    scatter) on torch's current stream, ordered against the asynchronous all-reduce exactly as the `torch._foreach_*`
+    calls that remain the path for everything else (CPU tensors over gloo); `hip=False` takes that path for GPU buckets
+    too (the A/B of DESIGN.md section 6).  Both give the same bits: `x * (1 / world)` is one fp32 multiply in either."""
+
+    def __init__(self, bucket_mb: float = 25.0, group=None, force: bool = False, hip: bool = True):
         self.bucket_bytes = int(bucket_mb * (1 << 20))
         self.group = group
         self.force = bool(force)
+        self.hip = bool(hip)
         self._flats: Dict[int, torch.Tensor] = {}
+        self._layouts: Dict[int, tuple] = {}
         self._pending: List[torch.Tensor] = []
         self._pending_bytes = 0
-        self._inflight: List[Tuple[torch.Tensor, List[torch.Tensor], object]] = []
+        # (flat buffer, its member views or None where the HIP kernels move the bucket, members, all-reduce handle)
+        self._inflight: List[Tuple[torch.Tensor, Optional[List[torch.Tensor]], List[torch.Tensor], object]] = []
         self.buckets_launched = 0
         # measurement (bench.py --mode train --gpus N): with `time_finish` every `finish()` is bracketed by HIP events on
         # the compute stream - what the step pays for the collectives that did NOT hide behind the backward (the wait
@@ -118,30 +130,73 @@ class BucketedGradReducer:
             if self._pending_bytes >= self.bucket_bytes:
                 self._launch()
 
-    def _flat_for(self, slot: int, members: List[torch.Tensor]) -> torch.Tensor:
+    def _flat_for(self, slot: int, members: List[torch.Tensor], n: Optional[int] = None) -> torch.Tensor:
         """the persistent flat buffer of the `slot`-th bucket of a step: the bucket composition is the same every step
         (the backward pushes the same tensors in the same order), so the buffer is allocated once and only re-made
-        when the total size or dtype / device changes - no `torch.cat` allocation per bucket per step"""
-        n = sum(t.numel() for t in members)
+        when the total size or dtype / device changes - no `torch.cat` allocation per bucket per step.  Allocated
+        zeroed: the HIP path pads every member's start to 16 bytes, and the all-reduce sums zeros in the padding."""
+        n = sum(t.numel() for t in members) if n is None else n
         flat = self._flats.get(slot)
         if flat is None or flat.numel() != n or flat.dtype != members[0].dtype or flat.device != members[0].device:
-            flat = torch.empty(n, dtype=members[0].dtype, device=members[0].device)
+            flat = torch.zeros(n, dtype=members[0].dtype, device=members[0].device)
             self._flats[slot] = flat
         return flat
+
+    def _hip_ok(self, members: List[torch.Tensor]) -> bool:
+        """the bucket kernels (csrc/bucket.hip) move non-empty contiguous fp32 tensors of one GPU; anything else (CPU
+        tensors over gloo, other dtypes) takes torch's multi-tensor ops"""
+        dev = members[0].device
+        return self.hip and dev.type == "cuda" and all(
+            t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.numel() > 0 for t in members)
+
+    def _tables(self, slot: int, members: List[torch.Tensor]):
+        """[(table, members in it, flat offset of its first member)], one entry per launch, and the padded length of
+        the bucket.  Only the layout is kept between steps; the pointers are read every step (`.grad` tensors are re-made
+        after `zero_grad(set_to_none=True)`) and travel in the kernel arguments."""
+        sizes = tuple(t.numel() for t in members)
+        cached = self._layouts.get(slot)
+        if cached is None or cached[0] != sizes:
+            launches, off = [], 0
+            for i in range(0, len(sizes), _lib.AMMC_BUCKET_MAX):
+                part, base, ends = sizes[i:i + _lib.AMMC_BUCKET_MAX], off, []
+                for n in part:
+                    off = (off + 3) & ~3
+                    off += n
+                    ends.append(off - base)
+                table = _lib.AmmcBucketTable()
+                table.end[:len(ends)] = ends
+                launches.append((table, i, len(part), base))
+                off = (off + 3) & ~3               # the next launch's `flat` stays 16-byte aligned
+            cached = (sizes, launches, off)
+            self._layouts[slot] = cached
+        for table, i, n, _ in cached[1]:
+            table.ptr[:n] = [t.data_ptr() for t in members[i:i + n]]
+        return cached[1], cached[2]
 
     def _launch(self) -> None:
         if not self._pending:
             return
         members = self._pending
-        flat = self._flat_for(len(self._inflight), members)
-        views, off = [], 0
-        for t in members:
-            n = t.numel()
-            views.append(flat[off:off + n].view_as(t))
-            off += n
-        torch._foreach_copy_(views, [t.detach() for t in members])          # one fused gather into the bucket
+        slot = len(self._inflight)
+        if self._hip_ok(members):
+            lib = _lib.load()
+            launches, total = self._tables(slot, members)
+            flat = self._flat_for(slot, members, total)
+            stream = torch.cuda.current_stream(flat.device).cuda_stream
+            for table, _, n, base in launches:                               # one gather launch per 128 members
+                _lib.check(lib.ammc_bucket_pack_f32(ctypes.byref(table), n, 4, flat.data_ptr() + 4 * base, stream),
+                           "bucket_pack")
+            views = None
+        else:
+            flat = self._flat_for(slot, members)
+            views, off = [], 0
+            for t in members:
+                n = t.numel()
+                views.append(flat[off:off + n].view_as(t))
+                off += n
+            torch._foreach_copy_(views, [t.detach() for t in members])      # one fused gather into the bucket
         work = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        self._inflight.append((views, members, work))
+        self._inflight.append((flat, views, members, work))
         self._pending, self._pending_bytes = [], 0
         self.buckets_launched += 1
 
@@ -152,13 +207,21 @@ class BucketedGradReducer:
         inv = 1.0 / self.world
         self.last_step_buckets = len(self._inflight)
         ev = None
-        if self.time_finish and self._inflight and self._inflight[0][0][0].is_cuda:
+        if self.time_finish and self._inflight and self._inflight[0][0].is_cuda:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        for views, members, work in self._inflight:
+        for slot, (flat, views, members, work) in enumerate(self._inflight):
             work.wait()
-            torch._foreach_mul_(views, inv)                                  # average in the bucket ...
-            torch._foreach_copy_([t.detach() for t in members], views)       # ... and scatter back in place
+            if views is None:                                                # the average and the scatter in one pass
+                lib = _lib.load()
+                launches, _ = self._tables(slot, members)
+                stream = torch.cuda.current_stream(flat.device).cuda_stream
+                for table, _, n, base in launches:
+                    _lib.check(lib.ammc_bucket_unpack_scale_f32(ctypes.byref(table), n, 4, flat.data_ptr() + 4 * base,
+                                                                inv, stream), "bucket_unpack_scale")
+            else:
+                torch._foreach_mul_(views, inv)                              # average in the bucket ...
+                torch._foreach_copy_([t.detach() for t in members], views)   # ... and scatter back in place
         if ev is not None:
             ev[1].record()
             self.finish_events.append(ev)

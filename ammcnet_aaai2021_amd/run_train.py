@@ -29,8 +29,32 @@ scheduler states, the sampler's RNG state, `g_step` and the arguments; `train_lo
 train_state, of the same stage only.  (The reference restarts `g_step` at 0 on a restart and saves no optimiser state:
 resuming here continues the learning-rate schedule and the Adam moments, a deliberate improvement.)
 
-One GPU per process: multi-GPU training from folders (per-rank banks and sampler streams, `parallel.BucketedGradReducer`)
-is not built yet.
+Several GPUs: one process per GPU under `torchrun` (or plain RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*), data parallel:
+
+    torchrun --nproc-per-node N -m ammcnet_aaai2021_amd.run_train --rgb_root DIR --op_root DIR --out RUN \
+        --iterations 80000 --batch 32 [--sync_stats] [--resume]
+
+  * `--batch` is the batch of ONE rank: the step trains on `world x batch` clips.  The learning rates are taken as
+    given - nothing is scaled with the world size; choose --lr_g / --lr_d for the global batch.
+  * ONE global sampler stream: every rank owns the same sampler (`--seed`), draws `world x batch` samples per iteration
+    and takes rows [rank * batch, (rank + 1) * batch).  The global batch of an N-rank run with per-rank batch b is, clip
+    for clip, the batch of a one-rank run with `--batch N*b` and the same seed; the train state holds one sampler state,
+    and a run may be resumed with another world as long as `world x batch` is unchanged (anything else is refused).
+  * Every rank fills its own FULL `ClipBank` (ShanghaiTech at 256 x 256 is ~126 GB: it fits one MI355X); `--workers` is
+    per rank.  A bank sharded over the ranks is the follow-up, not part of this entry.
+  * The models are built and seeded alike on every rank and then broadcast from rank 0 (`parallel.broadcast_state`);
+    gradients are averaged by one `parallel.BucketedGradReducer` per network, fed stage by stage by the backward.
+    BatchNorm and EMA-codebook statistics stay per rank (stock DDP semantics, see parallel.py) unless `--sync_stats`
+    shares them (`parallel.sync_statistics`): N ranks x b clips then compute the step of one rank on N*b clips.
+  * Rank 0 alone writes the checkpoints, the train state (it gains `world`) and the log, with a barrier behind every
+    save; without `--sync_stats` the saved buffers are rank 0's, and every rank continues from them (they are broadcast
+    at the save), so that a resumed run goes on exactly as the uninterrupted one.  Logged losses and PSNRs are means over the ranks;
+    `clips_per_s` counts the global batch; `skipped` counts the steps all ranks refused together.
+  * At every save and at the end a float64 checksum of all parameters is compared across the ranks (averaged gradients
+    and the fused Adam keep them bit-identical); ranks that disagree exit loudly, the `done` record says
+    `ranks_agree: true`.
+  * `--dist_backend gloo` lets several ranks share one GPU (RCCL refuses that): for tests.
+No run on more than one physical GPU has been measured yet.
 """
 from __future__ import annotations
 
@@ -41,7 +65,9 @@ import time
 
 import torch
 
-from . import harness, pipeline, synthetic
+import torch.distributed as dist
+
+from . import harness, parallel, pipeline, synthetic
 from .discriminator import PixelDiscriminator
 from .flownet import FlowNet2SD
 from .unet import get_twostream, get_unet_vq_topk_res
@@ -58,7 +84,7 @@ def parse(argv=None) -> argparse.Namespace:
     p.add_argument("--op_root", default=None, help="folder of sub-video folders of flows (.flo/.npy); joint, op")
     p.add_argument("--out", required=True, help="run folder: checkpoints, train state, train_log.jsonl")
     p.add_argument("--iterations", type=int, required=True)
-    p.add_argument("--batch", type=int, default=32)
+    p.add_argument("--batch", type=int, default=32, help="clips per rank and step (the global batch is world x batch)")
     p.add_argument("--size", type=int, default=256)
     p.add_argument("--embed_dim", type=int, default=64)
     p.add_argument("--n_embed", type=int, default=256)
@@ -76,13 +102,18 @@ def parse(argv=None) -> argparse.Namespace:
     p.add_argument("--flownet", default=None,
                    help="FlowNet2-SD .pth.tar (['state_dict']) or 'synthetic'; without it the flow term is off")
     p.add_argument("--seed", type=int, default=2017, help="sampler RandomState seed (the reference's 2017) and torch seed")
-    p.add_argument("--workers", type=int, default=8, help="decoder threads of the bank fill")
+    p.add_argument("--workers", type=int, default=8, help="decoder threads of the bank fill (per rank)")
     p.add_argument("--bank_budget_gb", type=float, default=None, help="default: 80%% of the free device memory")
     p.add_argument("--log_every", type=int, default=10)
     p.add_argument("--save_every", type=int, default=1000)
     p.add_argument("--resume", action="store_true")
     p.add_argument("--precision", choices=("s16", "fp32"), default="s16",
                    help="training kernels of the generator, discriminator and flow network")
+    p.add_argument("--dist_backend", choices=("nccl", "gloo"), default="nccl",
+                   help="process group of a multi-rank run: nccl (RCCL), or gloo so that ranks may share one GPU")
+    p.add_argument("--sync_stats", action="store_true",
+                   help="multi-rank: share the BatchNorm / EMA-codebook statistics (the step of ONE rank on world x batch "
+                        "clips); default: per-rank statistics")
     a = p.parse_args(argv)
     need = {"joint": ("rgb_root", "op_root"), "rgb": ("rgb_root",), "op": ("op_root",)}[a.stage]
     for root in ("rgb_root", "op_root"):
@@ -169,16 +200,69 @@ def save_all(out: str, G, D, state: dict, g_step: int) -> str:
     return harness.save_checkpoint(state, os.path.join(out, "train_state"), g_step)
 
 
+def rank_rows(drawn, rank: int, batch: int):
+    """rows [rank * batch, (rank + 1) * batch) of every array of a `world x batch` draw: this rank's clips of the step"""
+    return tuple(x[rank * batch:(rank + 1) * batch] for x in drawn)
+
+
+def check_resume_batch(state: dict, world: int, batch: int) -> None:
+    """A train state holds ONE sampler stream, consumed `world x batch` samples per iteration: it continues under any
+    world that keeps the global batch (2 x 2 -> 1 x 4 or 4 x 1), and under no other."""
+    saved_world, saved_batch = int(state.get("world", 1)), int(state["args"]["batch"])
+    if saved_world * saved_batch != world * batch:
+        raise SystemExit(f"--resume: the train state was written with a global batch of {saved_world * saved_batch} "
+                         f"(world {saved_world} x --batch {saved_batch}); this run has {world * batch} (world {world} x "
+                         f"--batch {batch}): the sampler stream and the schedule continue only under the same global batch")
+
+
+def params_checksum(*models) -> torch.Tensor:
+    """float64 [2]: the sum and the sum of squares of every parameter of `models`"""
+    ps = [p.detach().double() for m in models if m is not None for p in m.parameters()]
+    return torch.stack([torch.stack([p.sum() for p in ps]).sum(), torch.stack([(p * p).sum() for p in ps]).sum()])
+
+
+def ranks_agree(*models) -> bool:
+    """the desync guard: MIN and MAX of the parameter checksum over the ranks in one collective ([c, -c] under MAX)"""
+    c = params_checksum(*models)
+    both = torch.cat([c, -c])
+    dist.all_reduce(both, op=dist.ReduceOp.MAX)
+    hi, lo = both[:2], -both[2:]
+    return bool((hi == lo).all())
+
+
+def launch_world(env=None) -> int:
+    """WORLD_SIZE of the launch environment.  A multi-rank start names every process: WORLD_SIZE > 1 without RANK would
+    make each process rank 0 of a group nobody else joins (a wait until the rendezvous times out), so it is refused."""
+    env = os.environ if env is None else env
+    world = int(env.get("WORLD_SIZE", "1"))
+    if world > 1 and "RANK" not in env:
+        raise SystemExit(f"WORLD_SIZE={world} without RANK: run_train trains on one GPU per process - start one process per "
+                         "GPU with `torchrun --nproc-per-node N -m ammcnet_aaai2021_amd.run_train ...`, or set RANK, "
+                         "LOCAL_RANK and WORLD_SIZE (and MASTER_ADDR / MASTER_PORT) for each of them")
+    return world
+
+
 def main(argv=None) -> dict:
     a = parse(argv)
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("run_train trains on one GPU per process; multi-GPU training from folders (per-rank banks and "
-                         "sampler streams through parallel.BucketedGradReducer) is not built yet - run it without torchrun")
     if a.flownet and a.size % 64:
         raise SystemExit(f"--size {a.size}: FlowNet2-SD needs a multiple of 64 (drop --flownet to train without the flow term)")
+    launched = launch_world()
     if not torch.cuda.is_available():
         raise SystemExit("run_train needs a GPU: the HIP path has no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    rank, world, own_group = 0, 1, False
+    if launched > 1:
+        own_group = not dist.is_initialized()
+        rank, world, dev = parallel.init_distributed(a.dist_backend)
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        return _train(a, dev, rank, world)
+    finally:
+        if own_group and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def _train(a, dev, rank: int, world: int) -> dict:
     os.makedirs(a.out, exist_ok=True)
 
     bank = pipeline.ClipBank(a.rgb_root, a.op_root, a.size, dev, workers=a.workers, budget_gb=a.bank_budget_gb,
@@ -204,9 +288,19 @@ def main(argv=None) -> dict:
         G.load_state_dict(torch.load(os.path.join(a.out, "generator", name), map_location="cpu"), strict=True)
         if D is not None:
             D.load_state_dict(torch.load(os.path.join(a.out, "discriminator", name), map_location="cpu"), strict=True)
+        check_resume_batch(resumed, world, a.batch)
         g_step = int(resumed["g_step"])
         sampler.set_state(resumed["sampler"])
     G, D, flow_fn = to_device(G, D, F2, a, dev)
+    nets = [m for m in (G, D) if m is not None]
+    reducers = []
+    if world > 1:
+        for m in nets:                              # rank 0 wins; then one gradient reducer per network
+            parallel.broadcast_state(m, 0)
+            reducers.append(parallel.BucketedGradReducer())
+            parallel.attach_reducer(m, reducers[-1])
+        if a.sync_stats:
+            parallel.sync_statistics(G, True)
     opt_g = harness.adam(G.parameters(), lr=a.lr_g)
     sched_g = torch.optim.lr_scheduler.MultiStepLR(opt_g, milestones=a.milestones, gamma=0.5)
     opt_d = sched_d = None
@@ -224,11 +318,14 @@ def main(argv=None) -> dict:
 
     head = {"event": "start", "stage": a.stage, "g_step": g_step, "iterations": a.iterations, "rgb_frames": bank.n_rgb, "op_frames": bank.n_op,
             "sub_videos": len(bank.videos), "bank_GB": round(bank.nbytes / 1e9, 3), "fill_seconds": round(bank.fill_seconds, 3),
-            "workers": a.workers, "batch": a.batch, "size": a.size, "precision": a.precision,
+            "workers": a.workers, "batch": a.batch, "world": world, "global_batch": world * a.batch, "size": a.size,
+            "precision": a.precision, "sync_stats": bool(a.sync_stats and world > 1),
             "flow_term": ("off: no --flownet" if flow_fn is None else f"on ({a.flownet})"), "resumed": resumed is not None}
     log_path = os.path.join(a.out, "train_log.jsonl")
 
-    def emit(rec):
+    def emit(rec):                                  # rank 0 alone prints and writes
+        if rank != 0:
+            return
         line = json.dumps(rec)
         print(line, flush=True)
         with open(log_path, "a") as fp:
@@ -242,7 +339,8 @@ def main(argv=None) -> dict:
     t0 = time.perf_counter()
 
     def draw():                                     # the next iteration's global first frames, as `bank.gather` takes them
-        idx = bank.global_index(*sampler.draw(a.batch))
+        drawn = sampler.draw(world * a.batch)       # ONE global stream: every rank draws the step's whole batch
+        idx = bank.global_index(*(rank_rows(drawn, rank, a.batch) if world > 1 else drawn))
         return idx if a.stage == "joint" else (idx,)
     state_before = sampler.get_state()              # the RNG as it stands before the pending draw (what a resume restores)
     pending = draw()
@@ -271,6 +369,15 @@ def main(argv=None) -> dict:
             else:
                 psnr = {f"psnr_{a.stage}": harness.psnr_per_sample(outputs["pred"], clips[:, -1]).mean()}
                 terms = outputs["terms"]
+            # one read of the step's figures (below, behind the next draw); several ranks: their mean (equal batches: the mean over the global batch).
+            # A refused step is refused by all ranks together (`_FiniteWatch` votes), so all of them skip this collective
+            named = {"g_loss": gl} | ({"d_loss": dl} if D is not None else {}) | \
+                    ({f"g_{k}": v for k, v in terms.items()} if a.stage != "joint" else {}) | psnr
+            vals = torch.stack([v.detach().float().reshape(()) for v in named.values()])
+            if world > 1:
+                vals = vals.double()
+                dist.all_reduce(vals)
+                vals /= world
         # iteration g_step + 1's clips are drawn while the device runs this one
         th = time.perf_counter()
         state_before = sampler.get_state()
@@ -280,12 +387,13 @@ def main(argv=None) -> dict:
         if sched_d is not None:
             sched_d.step()
         if log_now:
-            rec = {"step": g_step, "g_loss": float(gl) if gl is not None else None}
+            figures = dict(zip(named, vals.tolist())) if gl is not None else {}
+            rec = {"step": g_step, "g_loss": figures["g_loss"] if gl is not None else None}
             if D is not None:
-                rec["d_loss"] = float(dl) if dl is not None else None
+                rec["d_loss"] = figures["d_loss"] if dl is not None else None
             if a.stage != "joint" and gl is not None:
-                rec.update({f"g_{k}": float(v) for k, v in terms.items()})
-            rec.update({n: float(psnr[n]) if gl is not None else None for n in psnr_names})
+                rec.update({k: v for k, v in figures.items() if k.startswith("g_") and k != "g_loss"})
+            rec.update({n: figures[n] if gl is not None else None for n in psnr_names})
             rec["lr_g"] = opt_g.param_groups[0]["lr"]
             if D is not None:
                 rec["lr_d"] = opt_d.param_groups[0]["lr"]
@@ -293,19 +401,35 @@ def main(argv=None) -> dict:
             n = g_step - it_last
             rec["ms_per_iter"] = round(1e3 * (now - t_last) / n, 3)
             rec["data_host_ms_per_iter"] = round(1e3 * (host_data_s - host_last) / n, 4)
+            rec["clips_per_s"] = round(world * a.batch * n / (now - t_last), 2)
+            rec["buckets"] = sum(r.last_step_buckets for r in reducers)
             rec["skipped"] = skipped
             t_last, it_last, host_last = now, g_step, host_data_s
             emit(rec)
             last = rec
         if g_step % a.save_every == 0 or g_step == a.iterations:
-            state = {"stage": a.stage, "g_step": g_step, "opt_g": opt_g.state_dict(), "sched_g": sched_g.state_dict(),
-                     "sampler": state_before, "skipped": skipped, "args": args_rec}
-            if D is not None:
-                state.update(opt_d=opt_d.state_dict(), sched_d=sched_d.state_dict())
-            save_all(a.out, G, D, state, g_step)
+            if world > 1 and not ranks_agree(*nets):
+                raise SystemExit(f"rank {rank}: the parameters differ between the ranks at step {g_step} (checksum MIN != MAX): "
+                                 "the run has desynchronised - nothing was saved for this step")
+            if rank == 0:
+                state = {"stage": a.stage, "g_step": g_step, "world": world, "opt_g": opt_g.state_dict(),
+                         "sched_g": sched_g.state_dict(), "sampler": state_before, "skipped": skipped, "args": args_rec}
+                if D is not None:
+                    state.update(opt_d=opt_d.state_dict(), sched_d=sched_d.state_dict())
+                save_all(a.out, G, D, state, g_step)
+            if world > 1:
+                # every rank goes on from what was saved: with per-rank statistics the saved buffers (BatchNorm running
+                # statistics, the EMA codebook the next forward reads) are rank 0's, and a resumed run, which loads them
+                # on every rank, must continue as this one does
+                for m in nets:
+                    parallel.broadcast_state(m, 0)
+                dist.barrier()                      # no rank runs ahead of a resume-visible state
     torch.cuda.synchronize()
     done = {"event": "done", "g_step": g_step, "seconds": round(time.perf_counter() - t0, 3), "skipped": skipped,
-            "fill_seconds": round(bank.fill_seconds, 3), "workers": a.workers, "last": last}
+            "fill_seconds": round(bank.fill_seconds, 3), "workers": a.workers, "world": world,
+            "ranks_agree": True if world == 1 else ranks_agree(*nets), "last": last}
+    if not done["ranks_agree"]:
+        raise SystemExit(f"rank {rank}: the parameters differ between the ranks at the end of the run (checksum MIN != MAX)")
     emit(done)
     return done
 

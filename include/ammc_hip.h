@@ -449,6 +449,29 @@ int ammc_gather_clips(const uint8_t* rgb_bank, int64_t n_rgb, const float* op_ba
 int ammc_gather_clips_one(const void* bank, int64_t n, int32_t kind, const int32_t* first, int32_t batch, int32_t len,
                           int32_t h, int32_t w, float* out, void* stream);
 
+/* Gradient buckets of data-parallel training (parallel.BucketedGradReducer; the reference is single-GPU): the gather of
+ * up to AMMC_BUCKET_MAX contiguous fp32 member tensors into one flat all-reduce buffer, and the way back with the
+ * average folded in, one launch each (torch._foreach_copy_ / _foreach_mul_ / _foreach_copy_ otherwise).
+ * table: HOST memory, read during the call only (it travels to the device in the kernel arguments: nothing is
+ *   uploaded and nothing on the device outlives the launch).  ptr[i]: device base of member i, 4-byte aligned;
+ *   end[i]: the flat offset, in floats, one past member i.  Member i starts at end[i - 1] (0 for i = 0), rounded up
+ *   to a multiple of `pad` floats: pad = 1 packs like torch.cat, pad = 4 starts every member on 16 bytes (the padding
+ *   floats are neither read nor written: allocate the flat buffer zeroed).  Members are non-empty (end[i] > start).
+ * flat: device, 4-byte (pad = 1) / 16-byte (pad = 4) aligned, end[n - 1] floats.
+ * pack:   flat[start_i + j] = member_i[j]
+ * unpack: member_i[j] = flat[start_i + j] * scale   (one fp32 multiply: bit-identical to mul_ followed by copy_)
+ * Runs whose two sides are congruent modulo 16 bytes move 16 bytes per lane, others float by float.  A bucket of more
+ * than AMMC_BUCKET_MAX members is several calls, each with `flat` advanced to its first member's start.
+ * AMMC_EINVAL: null / misaligned pointers, n outside [1, AMMC_BUCKET_MAX], pad not 1 or 4, an empty member. */
+#define AMMC_BUCKET_MAX 128
+typedef struct AmmcBucketTable {
+  void* ptr[AMMC_BUCKET_MAX];
+  int64_t end[AMMC_BUCKET_MAX];
+} AmmcBucketTable;
+int ammc_bucket_pack_f32(const AmmcBucketTable* table, int32_t n, int32_t pad, float* flat, void* stream);
+int ammc_bucket_unpack_scale_f32(const AmmcBucketTable* table, int32_t n, int32_t pad, const float* flat, float scale,
+                                 void* stream);
+
 /* nn.BatchNorm2d in training mode (unet.py:12,15).  Per-channel reductions write
  * partial[ammc_chan_reduce_blocks(B*H*W)][Q][C]; the finalizers combine them in fp64, fixed order. */
 int ammc_chan_reduce_blocks(int32_t pixels);
