@@ -268,13 +268,21 @@ def train_step(model: torch.nn.Module, optimizer: torch.optim.Optimizer, rgb: to
     b = rgb.shape[0]
     rgb_in = rgb[:, :-1].reshape(b, -1, *rgb.shape[-2:])
     op_in = op[:, :-1].reshape(b, -1, *op.shape[-2:])
+    return _generator_iteration(model, optimizer,
+                                lambda: (generator_loss(model(rgb_in, op_in), rgb[:, -1], op[:, -1], **lams), None))[0]
+
+
+def _generator_iteration(model: torch.nn.Module, optimizer, forward: Callable):
+    """The G-only iteration `train_step` and `train_step_single` share: `forward() -> (loss, kept)` runs the generator
+    and builds its loss; the verdict on the loss is taken before the backward is enqueued, the update is refused on a
+    non-finite one (`_FiniteWatch`).  -> (detached loss, kept)"""
     optimizer.zero_grad(set_to_none=True)
-    loss = generator_loss(model(rgb_in, op_in), rgb[:, -1], op[:, -1], **lams)
+    loss, kept = forward()
     vote, group = _watch_group(model)
     watch = _FiniteWatch(loss, group=group, vote=vote)
     loss.backward()
     watch.step(optimizer)
-    return loss.detach()
+    return loss.detach(), kept
 
 
 def _watch_group(*models):
@@ -395,28 +403,42 @@ def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, o
     op_in = op[:, :-1].reshape(b, -1, *op.shape[-2:])
     rgb_t, op_t = rgb[:, -1], op[:, -1]
     out = generator(rgb_in, op_in)
+    losses = _adversarial_iteration(
+        generator, discriminator, optimizer_G, optimizer_D, out[0], rgb_t, flow_fn,
+        lambda d_gen, flow_pred, flow_gt: generator_loss_full(out, rgb_t, op_t, d_gen, flow_pred, flow_gt, **lams))
+    if outputs is not None:
+        outputs["rgb"], outputs["op"] = out[0].detach(), out[1].detach()
+    return losses
+
+
+def _adversarial_iteration(generator, discriminator, optimizer_G, optimizer_D, pred: torch.Tensor, target: torch.Tensor,
+                           flow_fn: Optional[Callable], g_loss_fn: Callable):
+    """The schedule of one adversarial iteration behind the generator's forward, shared by `train_step_gan` and
+    `train_step_single_gan`: `pred` is the predicted frame / flow D sees (attached to the generator's graph), `target`
+    its ground truth, `g_loss_fn(d_gen, flow_pred, flow_gt) -> g_loss` the caller's generator loss (the flows are None
+    without `flow_fn`).  D is updated first, on (target, detached prediction); both updates are refused together on a
+    non-finite verdict.  -> the detached (g_loss, d_loss)"""
+    b = target.shape[0]
     vote, group = _watch_group(generator, discriminator)
-    # Round 6 (`AMMC_GAN_OVERLAP`, default on): the D update is independent of everything the generator still has to do - it
+    # `AMMC_GAN_OVERLAP` (default on): the D update is independent of everything the generator still has to do - it
     # reads the prediction detached, and the gradient that reaches G through D uses the filter packs of the `d_gen`
     # forward, not the live parameters - so its forward (beside FlowNet2-SD and the `d_gen` forward), its backward and its
     # Adam step (beside the generator's backward, whose BatchNorm passes leave the matrix pipe idle: the two-stream argument
-    # of DESIGN.md section 4) run on a SECOND HIP stream.  Same kernels, same order on each stream: every number is what
-    # the serial form computes.  Off with a gradient reducer / synchronised statistics attached (their collectives are
-    # ordered on the caller's stream) and on the CPU.
-    overlap = GAN_OVERLAP and out[0].is_cuda and not vote and getattr(discriminator, "_grad_reducer", None) is None
-    main = torch.cuda.current_stream(out[0].device) if overlap else None
-    lane = _gan_side_stream(out[0].device) if overlap else None
-
-    def d_forward():
+    # of DESIGN.md section 4) run on a SECOND HIP stream, forked right behind the generator's forward.  Same kernels, same
+    # order on each stream: every number is what the serial form computes.  Off with a gradient reducer / synchronised
+    # statistics attached (their collectives are ordered on the caller's stream) and on the CPU.
+    overlap = GAN_OVERLAP and pred.is_cuda and not vote and getattr(discriminator, "_grad_reducer", None) is None
+    main = torch.cuda.current_stream(pred.device) if overlap else None
+    lane = _gan_side_stream(pred.device) if overlap else None
+    on_lane = (lambda: torch.cuda.stream(lane)) if overlap else contextlib.nullcontext
+    if overlap:
+        lane.wait_stream(main)
+    with on_lane():
         # D(real) and D(fake.detach()) (train_helper.py:326-327) as one call on 2 b frames: the discriminator has no
         # batch-coupled layer, the patch maps and every gradient are those of the two calls
-        d_both_ = discriminator(torch.cat([rgb_t, out[0].detach()]))
-        return d_both_, discriminate_loss(d_both_[:b], d_both_[b:]), getattr(discriminator, "last_overflow", None)
-    early = overlap and GAN_OVERLAP_EARLY
-    if early:
-        lane.wait_stream(main)
-        with torch.cuda.stream(lane):
-            d_both, d_loss, d_flag = d_forward()
+        d_both = discriminator(torch.cat([target, pred.detach()]))
+        d_loss = discriminate_loss(d_both[:b], d_both[b:])
+        d_flag = getattr(discriminator, "last_overflow", None)
     flow_pred = flow_gt = None
     flow_mods = [m for m in (getattr(flow_fn, "__self__", None), getattr(flow_fn, "net", None)) if m is not None]
     if flow_fn is not None:
@@ -425,22 +447,17 @@ def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, o
             # (train_helper.py:299, 309-312), not with the frame before it: followed as written.  The two FlowNet2-SD
             # forwards run as ONE batch of 2 b pairs (every sample is independent in that network - its mean subtraction
             # is per sample - so the flows are the same; the layers below 1/16 resolution fill the chip twice as well)
-            both = flow_fn(torch.cat([rgb[:, -1], rgb[:, -1]]), torch.cat([out[0].detach(), rgb_t]))
+            both = flow_fn(torch.cat([target, target]), torch.cat([pred.detach(), target]))
             flow_pred, flow_gt = both[:b], both[b:]
     d_params = [p for p in discriminator.parameters() if p.requires_grad]
     for p in d_params:                 # the G step needs dL/d(frame) through D, not D's weight gradients
         p.requires_grad_(False)
     try:
-        d_gen = discriminator(out[0])
+        d_gen = discriminator(pred)
     finally:
         for p in d_params:
             p.requires_grad_(True)
-    g_loss = generator_loss_full(out, rgb_t, op_t, d_gen, flow_pred, flow_gt, **lams)
-    if not early:
-        if overlap:
-            lane.wait_stream(main)
-        with (torch.cuda.stream(lane) if overlap else contextlib.nullcontext()):
-            d_both, d_loss, d_flag = d_forward()
+    g_loss = g_loss_fn(d_gen, flow_pred, flow_gt)
     if overlap:
         main.wait_stream(lane)                     # (the verdict below reads d_loss on the caller's stream)
         for t in (d_both, d_loss) + ((d_flag,) if d_flag is not None else ()):
@@ -449,7 +466,7 @@ def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, o
     # estimator join the verdict: `s16_guard = "defer"` on those modules leaves them on the device instead of syncing)
     watch = _FiniteWatch(d_loss, g_loss, group=group, vote=vote,
                          flags=[d_flag] + [getattr(m, "last_overflow", None) for m in flow_mods])
-    with (torch.cuda.stream(lane) if overlap else contextlib.nullcontext()):
+    with on_lane():
         optimizer_D.zero_grad(set_to_none=True)
         d_loss.backward()                          # (autograd runs it on the stream of its forward: the lane)
         watch.step(optimizer_D)
@@ -458,18 +475,16 @@ def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, o
     optimizer_G.step()
     if overlap:
         main.wait_stream(lane)                     # successors on the caller's stream see both updates
-    if outputs is not None:
-        outputs["rgb"], outputs["op"] = out[0].detach(), out[1].detach()
     return g_loss.detach(), d_loss.detach()
 
 
 # (the two FlowNet2-SD forwards on a third stream, their no-gradient term joined to the loss value at the end, were built and
 # measured as well: 80.2 / 80.4 ms against 80.2 / 79.3 - nothing; removed)
-# AMMC_GAN_OVERLAP: 2 (default) = the D lane starts right behind the generator's forward (its own forward beside FlowNet2-SD and
-# the d_gen forward: 79.84 / 80.20 / 79.85 -> 79.04 / 78.82 / 78.88 ms against 1), 1 = it starts behind g_loss (the first form:
-# 81.69 / 81.59 -> 78.94 / 79.19 against 0), 0 = serial
-GAN_OVERLAP = os.environ.get("AMMC_GAN_OVERLAP", "2") != "0"
-GAN_OVERLAP_EARLY = os.environ.get("AMMC_GAN_OVERLAP", "2") == "2"
+# AMMC_GAN_OVERLAP: on (default; any value but 0) = the D lane starts right behind the generator's forward (its own forward
+# beside FlowNet2-SD and the d_gen forward), 0 = serial.  A late form, the lane starting behind g_loss, came first (81.69 /
+# 81.59 -> 78.94 / 79.19 ms against serial); the present one beat it, 79.84 / 80.20 / 79.85 -> 79.04 / 78.82 / 78.88 ms, and
+# the late form was retired after that A/B: it lives in the history of this file.
+GAN_OVERLAP = os.environ.get("AMMC_GAN_OVERLAP", "1") != "0"
 _GAN_LANES: Dict = {}
 
 
@@ -539,57 +554,15 @@ def train_step_single_gan(generator: torch.nn.Module, discriminator: torch.nn.Mo
     x = clips[:, :-1].reshape(b, -1, *clips.shape[-2:])
     target = clips[:, -1]
     pred, diff, _ = generator(x)
-    vote, group = _watch_group(generator, discriminator)
-    overlap = GAN_OVERLAP and pred.is_cuda and not vote and getattr(discriminator, "_grad_reducer", None) is None
-    main = torch.cuda.current_stream(pred.device) if overlap else None
-    lane = _gan_side_stream(pred.device) if overlap else None
+    kept = {}
 
-    def d_forward():
-        d_both_ = discriminator(torch.cat([target, pred.detach()]))      # D(real) and D(fake.detach()) as one call
-        return d_both_, discriminate_loss(d_both_[:b], d_both_[b:]), getattr(discriminator, "last_overflow", None)
-    early = overlap and GAN_OVERLAP_EARLY
-    if early:
-        lane.wait_stream(main)
-        with torch.cuda.stream(lane):
-            d_both, d_loss, d_flag = d_forward()
-    flow_pred = flow_gt = None
-    flow_mods = [m for m in (getattr(flow_fn, "__self__", None), getattr(flow_fn, "net", None)) if m is not None]
-    if flow_fn is not None:
-        with torch.no_grad():          # (target, prediction) and (target, target), one batch of 2 b pairs
-            both = flow_fn(torch.cat([target, target]), torch.cat([pred.detach(), target]))
-            flow_pred, flow_gt = both[:b], both[b:]
-    d_params = [p for p in discriminator.parameters() if p.requires_grad]
-    for p in d_params:
-        p.requires_grad_(False)
-    try:
-        d_gen = discriminator(pred)
-    finally:
-        for p in d_params:
-            p.requires_grad_(True)
-    g_loss, terms = single_stream_loss(stream, pred, target, diff, d_gen, flow_pred, flow_gt, **lams)
-    if not early:
-        if overlap:
-            lane.wait_stream(main)
-        with (torch.cuda.stream(lane) if overlap else contextlib.nullcontext()):
-            d_both, d_loss, d_flag = d_forward()
-    if overlap:
-        main.wait_stream(lane)
-        for t in (d_both, d_loss) + ((d_flag,) if d_flag is not None else ()):
-            t.record_stream(main)
-    watch = _FiniteWatch(d_loss, g_loss, group=group, vote=vote,
-                         flags=[d_flag] + [getattr(m, "last_overflow", None) for m in flow_mods])
-    with (torch.cuda.stream(lane) if overlap else contextlib.nullcontext()):
-        optimizer_D.zero_grad(set_to_none=True)
-        d_loss.backward()
-        watch.step(optimizer_D)
-    optimizer_G.zero_grad(set_to_none=True)
-    g_loss.backward()
-    optimizer_G.step()
-    if overlap:
-        main.wait_stream(lane)
+    def g_loss_fn(d_gen, flow_pred, flow_gt):
+        g_loss, kept["terms"] = single_stream_loss(stream, pred, target, diff, d_gen, flow_pred, flow_gt, **lams)
+        return g_loss
+    losses = _adversarial_iteration(generator, discriminator, optimizer_G, optimizer_D, pred, target, flow_fn, g_loss_fn)
     if outputs is not None:
-        outputs["pred"], outputs["terms"] = pred.detach(), {k: v.detach() for k, v in terms.items()}
-    return g_loss.detach(), d_loss.detach()
+        outputs["pred"], outputs["terms"] = pred.detach(), {k: v.detach() for k, v in kept["terms"].items()}
+    return losses
 
 
 def train_step_single(generator: torch.nn.Module, optimizer_G, clips: torch.Tensor, outputs: Optional[dict] = None,
@@ -605,16 +578,15 @@ def train_step_single(generator: torch.nn.Module, optimizer_G, clips: torch.Tens
     lams = {k: v for k, v in lams.items() if k != "lam_adv_op"}
     x = clips[:, :-1].reshape(b, -1, *clips.shape[-2:])
     target = clips[:, -1]
-    optimizer_G.zero_grad(set_to_none=True)
-    pred, diff, _ = generator(x)
-    loss, terms = single_stream_loss("op", pred, target, diff, **lams)
-    vote, group = _watch_group(generator)
-    watch = _FiniteWatch(loss, group=group, vote=vote)
-    loss.backward()
-    watch.step(optimizer_G)
+
+    def forward():
+        pred, diff, _ = generator(x)
+        loss, terms = single_stream_loss("op", pred, target, diff, **lams)
+        return loss, (pred, terms)
+    loss, (pred, terms) = _generator_iteration(generator, optimizer_G, forward)
     if outputs is not None:
         outputs["pred"], outputs["terms"] = pred.detach(), {k: v.detach() for k, v in terms.items()}
-    return loss.detach()
+    return loss
 
 
 # ---- score fusion and frame-level AUC (the step after the records) ------------------------------

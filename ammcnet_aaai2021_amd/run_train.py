@@ -267,14 +267,6 @@ def _train(a, dev, rank: int, world: int) -> dict:
 
     bank = pipeline.ClipBank(a.rgb_root, a.op_root, a.size, dev, workers=a.workers, budget_gb=a.bank_budget_gb,
                              rgb_len=harness.RGB_LEN_CLIP, op_len=harness.OP_LEN_CLIP)
-    if a.stage == "joint":
-        sampler = pipeline.ClipSampler(bank.rgb_count, bank.op_count, harness.RGB_LEN_CLIP, harness.OP_LEN_CLIP,
-                                       seed=a.seed)
-    elif a.stage == "rgb":
-        sampler = pipeline.SingleClipSampler(bank.rgb_count, harness.RGB_LEN_CLIP, seed=a.seed, what="rgb")
-    else:
-        sampler = pipeline.SingleClipSampler(bank.op_count, harness.OP_LEN_CLIP, seed=a.seed, what="op")
-
     G, D, F2 = build_models(a)
     g_step, resumed = 0, None
     if a.resume:
@@ -290,7 +282,6 @@ def _train(a, dev, rank: int, world: int) -> dict:
             D.load_state_dict(torch.load(os.path.join(a.out, "discriminator", name), map_location="cpu"), strict=True)
         check_resume_batch(resumed, world, a.batch)
         g_step = int(resumed["g_step"])
-        sampler.set_state(resumed["sampler"])
     G, D, flow_fn = to_device(G, D, F2, a, dev)
     nets = [m for m in (G, D) if m is not None]
     reducers = []
@@ -316,6 +307,35 @@ def _train(a, dev, rank: int, world: int) -> dict:
     lams = lams_of(a)
     args_rec = {k: v for k, v in vars(a).items()}
 
+    # the stage, resolved once: its sampler, its step (-> g_loss, d_loss or None), how its train PSNRs are read from the
+    # step's outputs and clips (joint: clips = (rgb, op); a single stage: its clips), and whether it logs its loss terms
+    if a.stage == "joint":
+        sampler = pipeline.ClipSampler(bank.rgb_count, bank.op_count, harness.RGB_LEN_CLIP, harness.OP_LEN_CLIP,
+                                       seed=a.seed)
+        psnr_names, log_terms = ("psnr_rgb", "psnr_op"), False
+
+        def step(clips, outputs):
+            return harness.train_step_gan(G, D, opt_g, opt_d, *clips, flow_fn, outputs=outputs, **lams)
+
+        def psnr_pairs(outputs, clips):
+            return (outputs["rgb"], clips[0][:, -1]), (outputs["op"], clips[1][:, -1])
+    else:
+        count, clip_len = (bank.rgb_count, harness.RGB_LEN_CLIP) if a.stage == "rgb" else (bank.op_count, harness.OP_LEN_CLIP)
+        sampler = pipeline.SingleClipSampler(count, clip_len, seed=a.seed, what=a.stage)
+        psnr_names, log_terms = (f"psnr_{a.stage}",), True
+
+        if D is None:
+            def step(clips, outputs):
+                return harness.train_step_single(G, opt_g, clips, outputs=outputs, **lams), None
+        else:
+            def step(clips, outputs):
+                return harness.train_step_single_gan(G, D, opt_g, opt_d, clips, flow_fn, outputs=outputs, **lams)
+
+        def psnr_pairs(outputs, clips):
+            return ((outputs["pred"], clips[:, -1]),)
+    if resumed is not None:
+        sampler.set_state(resumed["sampler"])
+
     head = {"event": "start", "stage": a.stage, "g_step": g_step, "iterations": a.iterations, "rgb_frames": bank.n_rgb, "op_frames": bank.n_op,
             "sub_videos": len(bank.videos), "bank_GB": round(bank.nbytes / 1e9, 3), "fill_seconds": round(bank.fill_seconds, 3),
             "workers": a.workers, "batch": a.batch, "world": world, "global_batch": world * a.batch, "size": a.size,
@@ -332,7 +352,6 @@ def _train(a, dev, rank: int, world: int) -> dict:
             fp.write(line + "\n")
 
     emit(head)
-    psnr_names = ("psnr_rgb", "psnr_op") if a.stage == "joint" else (f"psnr_{a.stage}",)
     skipped = 0
     host_data_s = 0.0
     t_last, it_last, host_last = time.perf_counter(), g_step, 0.0
@@ -341,7 +360,7 @@ def _train(a, dev, rank: int, world: int) -> dict:
     def draw():                                     # the next iteration's global first frames, as `bank.gather` takes them
         drawn = sampler.draw(world * a.batch)       # ONE global stream: every rank draws the step's whole batch
         idx = bank.global_index(*(rank_rows(drawn, rank, a.batch) if world > 1 else drawn))
-        return idx if a.stage == "joint" else (idx,)
+        return idx if isinstance(idx, tuple) else (idx,)
     state_before = sampler.get_state()              # the RNG as it stands before the pending draw (what a resume restores)
     pending = draw()
     last = None
@@ -353,26 +372,16 @@ def _train(a, dev, rank: int, world: int) -> dict:
         host_data_s += time.perf_counter() - th
         outputs = {} if log_now else None
         try:
-            if a.stage == "joint":
-                gl, dl = harness.train_step_gan(G, D, opt_g, opt_d, *clips, flow_fn, outputs=outputs, **lams)
-            elif D is not None:
-                gl, dl = harness.train_step_single_gan(G, D, opt_g, opt_d, clips, flow_fn, outputs=outputs, **lams)
-            else:
-                gl, dl = harness.train_step_single(G, opt_g, clips, outputs=outputs, **lams), None
+            gl, dl = step(clips, outputs)
         except FloatingPointError:
             skipped += 1                            # `_FiniteWatch` refused the step: no update of either network
             gl = dl = None
         if log_now and gl is not None:              # (the outputs may alias engine buffers: read them before the next step)
-            if a.stage == "joint":
-                psnr = {"psnr_rgb": harness.psnr_per_sample(outputs["rgb"], clips[0][:, -1]).mean(),
-                        "psnr_op": harness.psnr_per_sample(outputs["op"], clips[1][:, -1]).mean()}
-            else:
-                psnr = {f"psnr_{a.stage}": harness.psnr_per_sample(outputs["pred"], clips[:, -1]).mean()}
-                terms = outputs["terms"]
+            psnr = {n: harness.psnr_per_sample(gen, gt).mean() for n, (gen, gt) in zip(psnr_names, psnr_pairs(outputs, clips))}
             # one read of the step's figures (below, behind the next draw); several ranks: their mean (equal batches: the mean over the global batch).
             # A refused step is refused by all ranks together (`_FiniteWatch` votes), so all of them skip this collective
             named = {"g_loss": gl} | ({"d_loss": dl} if D is not None else {}) | \
-                    ({f"g_{k}": v for k, v in terms.items()} if a.stage != "joint" else {}) | psnr
+                    ({f"g_{k}": v for k, v in outputs["terms"].items()} if log_terms else {}) | psnr
             vals = torch.stack([v.detach().float().reshape(()) for v in named.values()])
             if world > 1:
                 vals = vals.double()
@@ -391,7 +400,7 @@ def _train(a, dev, rank: int, world: int) -> dict:
             rec = {"step": g_step, "g_loss": figures["g_loss"] if gl is not None else None}
             if D is not None:
                 rec["d_loss"] = figures["d_loss"] if dl is not None else None
-            if a.stage != "joint" and gl is not None:
+            if log_terms and gl is not None:
                 rec.update({k: v for k, v in figures.items() if k.startswith("g_") and k != "g_loss"})
             rec.update({n: figures[n] if gl is not None else None for n in psnr_names})
             rec["lr_g"] = opt_g.param_groups[0]["lr"]

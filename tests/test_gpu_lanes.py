@@ -1,7 +1,9 @@
-"""The two concurrency switches that are ON by default - the eval forward's two network streams on two HIP streams
-(engine.EVAL_LANES, AMMC_EVAL_LANES) and the training step's rgb / flow halves on two HIP streams (train.TWO_STREAMS,
-AMMC_TWO_STREAMS) - against the same launches on ONE stream.  Same kernels, disjoint buffers: the forward outputs and
-buffers must be BIT-identical; gradients that end in fp32 atomics are held to the run-to-run noise of one configuration."""
+"""The three concurrency switches that are ON by default - the eval forward's two network streams on two HIP streams
+(engine.EVAL_LANES, AMMC_EVAL_LANES), the training step's rgb / flow halves on two HIP streams (train.TWO_STREAMS,
+AMMC_TWO_STREAMS) and the adversarial iteration's D update on a second HIP stream (harness.GAN_OVERLAP,
+AMMC_GAN_OVERLAP) - against the same launches on ONE stream.  Same kernels, disjoint buffers: the forward outputs, the
+losses and the buffers must be BIT-identical; gradients that end in fp32 atomics are held to the run-to-run noise of one
+configuration."""
 import numpy as np
 import pytest
 import torch
@@ -77,3 +79,59 @@ def test_training_two_streams_on_equals_off(hw, batch):
         # (some weight gradients are accumulated with fp32 atomics: their run-to-run noise on ONE stream is the gate)
         noise = float((off[1][n] - off2[1][n]).abs().max())
         assert float((on[1][n] - off[1][n]).abs().max()) <= max(4.0 * noise, 0.0) + 1e-7 * float(off[1][n].abs().max()), n
+
+
+def _gan_once(case, overlap: bool, monkeypatch, hw=64, batch=2):
+    """one adversarial iteration (lr 0: both steps run, the gradients stay readable) with the D lane on / off ->
+    (g_loss, d_loss, predicted frames, gradients of G and D, times the side stream was requested)"""
+    requested = []
+    real = Hn._gan_side_stream
+    monkeypatch.setattr(Hn, "GAN_OVERLAP", overlap)
+    monkeypatch.setattr(Hn, "_gan_side_stream", lambda *a, **k: (requested.append(a), real(*a, **k))[1])
+    try:
+        rgb_x, op_x, rgb_t, op_t = S.make_clips(batch, hw, hw, tag=f"lanes-gan-{case}")
+        rgb = torch.cat([rgb_x.view(batch, 4, 3, hw, hw), rgb_t[:, None]], 1).to(DEV)
+        op = torch.cat([op_x.view(batch, 3, 2, hw, hw), op_t[:, None]], 1).to(DEV)
+        if case == "joint":
+            G = A.get_twostream((12, 6), (3, 2), 64, 256, 2)
+            G.load_state_dict(S.make_twostream_state())
+        else:
+            G = A.get_unet_vq_topk_res(12, 3, 64, 256, 2)
+            G.load_state_dict({k[4:]: v for k, v in S.make_twostream_state().items() if k.startswith("rgb.")})
+        D = A.PixelDiscriminator(3, [128, 256, 512, 512])
+        D.load_state_dict(S.make_discriminator_state())
+        F2 = A.FlowNet2SD()
+        F2.load_state_dict(S.make_flownet2sd_state())
+        G, D, F2 = G.to(DEV).train(), D.to(DEV).train(), F2.to(DEV).eval()
+        opt_g, opt_d = torch.optim.SGD(G.parameters(), lr=0.0), torch.optim.SGD(D.parameters(), lr=0.0)
+        out = {}
+        if case == "joint":
+            gl, dl = Hn.train_step_gan(G, D, opt_g, opt_d, rgb, op, Hn.flownet_flow_fn(F2), outputs=out)
+            preds = (out["rgb"].clone(), out["op"].clone())
+        else:
+            gl, dl = Hn.train_step_single_gan(G, D, opt_g, opt_d, rgb, Hn.flownet_flow_fn(F2), outputs=out)
+            preds = (out["pred"].clone(),)
+        torch.cuda.synchronize()
+        grads = {"G." + n: p.grad.detach().clone() for n, p in G.named_parameters()}
+        grads.update({"D." + n: p.grad.detach().clone() for n, p in D.named_parameters()})
+        return gl.clone(), dl.clone(), preds, grads, len(requested)
+    finally:
+        monkeypatch.undo()
+
+
+@pytest.mark.parametrize("case", ["joint", "rgb"])
+def test_gan_overlap_on_equals_off(case, monkeypatch):
+    """`train_step_gan` (twostream + PixelDiscriminator(3) + FlowNet2-SD) and `train_step_single_gan` (the rgb stage with
+    its flow term) at 64 x 64, the smallest frame FlowNet2-SD takes: every fork / join of the D lane exists"""
+    on = _gan_once(case, True, monkeypatch)
+    off = _gan_once(case, False, monkeypatch)
+    off2 = _gan_once(case, False, monkeypatch)
+    assert on[4] == 1 and off[4] == 0 and off2[4] == 0           # the switch did switch
+    print(f"{case}: g_loss on/off {float(on[0])!r} {float(off[0])!r}  d_loss on/off {float(on[1])!r} {float(off[1])!r}")
+    assert torch.equal(on[0], off[0]) and torch.equal(on[1], off[1])
+    assert len(on[2]) == len(off[2]) and all(torch.equal(a, b) for a, b in zip(on[2], off[2]))
+    assert sorted(on[3]) == sorted(off[3])
+    for n in off[3]:
+        # (some weight gradients are accumulated with fp32 atomics: their run-to-run noise on ONE stream is the gate)
+        noise = float((off[3][n] - off2[3][n]).abs().max())
+        assert float((on[3][n] - off[3][n]).abs().max()) <= max(4.0 * noise, 0.0) + 1e-7 * float(off[3][n].abs().max()), n
