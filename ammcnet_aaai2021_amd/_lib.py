@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AMMC_LIB: another build of the SAME library (A/B measurements: `python -m ammcnet_aaai2021_amd.build --variant x`)
 LIB_PATH = os.environ.get("AMMC_LIB") or os.path.join(HERE, "libammc_hip.so")
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_LRELU = 0, 1, 2, 3
 
@@ -50,6 +50,8 @@ class AmmcWgradDesc(C.Structure):
 
 
 AMMC_BUCKET_MAX = 128
+AMMC_PRED_LOSS_ROWS = 4      # image rows per partial row of ammc_pred_loss_fwd_f32 (include/ammc_hip.h)
+AMMC_L1_CHUNK = 4096         # elements per partial of ammc_l1_partials_f32
 
 
 class AmmcBucketTable(C.Structure):
@@ -160,6 +162,10 @@ SIGNATURES = {
     "ammc_codebook_count_f32": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "ammc_codebook_ema_apply_f32": (C.c_int, [_p, _p, _i32, _i32, _f32, _f32, _f32, _p, _p, _p, _p]),
     "ammc_codebook_ema_f32": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _p, _p, _p, _p]),
+    "ammc_pred_loss_partial_rows": (C.c_int, [_i32, _i32, _i32]),
+    "ammc_pred_loss_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "ammc_pred_loss_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "ammc_l1_partials_f32": (C.c_int, [_p, _p, _i64, _p, _p]),
 }
 
 _lib = None

@@ -242,9 +242,23 @@ class _Done:
         pass
 
 
+# AMMC_FUSED_LOSS: 1 = the per-pixel terms of the generator's objective (intensity, gradient difference, flow) come from the
+# library's loss kernels (`losses.py`: one forward and one backward launch per prediction pair), 0 (default) = the torch
+# chains below.  Device tensors only: on the CPU the flag changes nothing.  profiles/loss_ab.txt holds the A/B.
+FUSED_LOSS = os.environ.get("AMMC_FUSED_LOSS", "0") not in ("", "0")
+
+
+def _fused(*tensors) -> bool:
+    return FUSED_LOSS and all(t is not None and t.is_cuda for t in tensors)
+
+
 def generator_loss(out, rgb_t: torch.Tensor, op_t: torch.Tensor, lam_lp: float = 1.0, lam_lp_op: float = 1.0,
                    lam_latent: float = 1.0) -> torch.Tensor:
     rgb, op, (rd, od), _ = out[:4]
+    if _fused(rgb, op, rgb_t, op_t):
+        from . import losses
+        return lam_lp * losses.prediction_terms(rgb, rgb_t, False)[0] + \
+            lam_lp_op * losses.prediction_terms(op, op_t, False)[0] + lam_latent * (rd + od).sum()
     l_rgb = torch.norm(rgb - rgb_t, p=2, dim=1).mean()            # `L2`, losses_utils.py:124-129
     l_op = torch.norm(op - op_t, p=2, dim=1).mean()
     return lam_lp * l_rgb + lam_lp_op * l_op + lam_latent * (rd + od).sum()
@@ -382,11 +396,30 @@ def generator_loss_full(out, rgb_t, op_t, d_gen, flow_pred=None, flow_gt=None, l
     """`Twostream_vq_Loss.forward` (loss_zoo.py:310-336); the FlowNet2-SD term enters only through precomputed
     flows"""
     rgb = out[0]
+    if _fused(rgb, out[1], rgb_t, op_t):
+        from . import losses
+        # each prediction pair is visited once: the rgb pair's two terms in one forward (and one backward) launch
+        l_rgb, l_gdl = losses.prediction_terms(rgb, rgb_t, True)
+        l_op, _ = losses.prediction_terms(out[1], op_t, False)
+        rd, od = out[2]
+        loss = lam_lp * l_rgb + lam_lp_op * l_op + lam_latent * (rd + od).sum() + lam_adv * adversarial_loss(d_gen) + \
+            lam_gdl * l_gdl
+        if flow_pred is not None:
+            loss = loss + lam_flow * _flow_term(flow_pred, flow_gt)
+        return loss
     loss = generator_loss(out, rgb_t, op_t, lam_lp, lam_lp_op, lam_latent) + lam_adv * adversarial_loss(d_gen) + \
         lam_gdl * gradient_loss(rgb, rgb_t)
     if flow_pred is not None:
         loss = loss + lam_flow * flow_loss(flow_pred, flow_gt)
     return loss
+
+
+def _flow_term(flow_pred: torch.Tensor, flow_gt: torch.Tensor) -> torch.Tensor:
+    """`flow_loss` under `FUSED_LOSS`: the value-only kernel where no gradient is wanted (flows out of a `no_grad` block)"""
+    if _fused(flow_pred, flow_gt) and not (flow_pred.requires_grad or flow_gt.requires_grad):
+        from . import losses
+        return losses.l1_mean(flow_pred.contiguous(), flow_gt.contiguous())
+    return flow_loss(flow_pred, flow_gt)
 
 
 def train_step_gan(generator: torch.nn.Module, discriminator: torch.nn.Module, optimizer_G, optimizer_D,
@@ -519,14 +552,20 @@ def single_stream_loss(stream: str, pred, target, diff, d_gen=None, flow_pred=No
     if unknown:
         raise TypeError(f"the {stream} stage has no loss weight {sorted(unknown)} (it takes {sorted(SINGLE_LAMS[stream])})")
     lam = {**SINGLE_LAMS[stream], **lams}
-    t = {"int": torch.norm(pred - target, p=2, dim=1).mean(), "latent": diff.sum()}
+    if stream == "rgb" and d_gen is None:
+        raise ValueError("the rgb stage's loss has an adversarial term: it needs the discriminator's output")
+    if _fused(pred, target):
+        from . import losses
+        l_int, l_gdl = losses.prediction_terms(pred, target, stream == "rgb")
+        t = {"int": l_int, "latent": diff.sum()}
+    else:
+        l_gdl = None
+        t = {"int": torch.norm(pred - target, p=2, dim=1).mean(), "latent": diff.sum()}
     if stream == "rgb":
-        if d_gen is None:
-            raise ValueError("the rgb stage's loss has an adversarial term: it needs the discriminator's output")
-        t["adv"], t["gdl"] = adversarial_loss(d_gen), gradient_loss(pred, target)
+        t["adv"], t["gdl"] = adversarial_loss(d_gen), (l_gdl if l_gdl is not None else gradient_loss(pred, target))
         loss = lam["lam_adv"] * t["adv"] + lam["lam_gdl"] * t["gdl"]
         if flow_pred is not None:
-            t["flow"] = flow_loss(flow_pred, flow_gt)
+            t["flow"] = _flow_term(flow_pred, flow_gt)
             loss = loss + lam["lam_flow"] * t["flow"]
         loss = loss + lam["lam_lp"] * t["int"]
     else:

@@ -114,6 +114,9 @@ def parse(argv=None) -> argparse.Namespace:
     p.add_argument("--sync_stats", action="store_true",
                    help="multi-rank: share the BatchNorm / EMA-codebook statistics (the step of ONE rank on world x batch "
                         "clips); default: per-rank statistics")
+    p.add_argument("--fused_loss", action="store_true",
+                   help="the intensity / gradient-difference / flow terms of the loss on the library's fused kernels "
+                        "(harness.FUSED_LOSS; also AMMC_FUSED_LOSS=1), any --stage; default: the torch chains")
     a = p.parse_args(argv)
     need = {"joint": ("rgb_root", "op_root"), "rgb": ("rgb_root",), "op": ("op_root",)}[a.stage]
     for root in ("rgb_root", "op_root"):
@@ -305,6 +308,8 @@ def _train(a, dev, rank: int, world: int) -> dict:
             opt_d.load_state_dict(resumed["opt_d"])
             sched_d.load_state_dict(resumed["sched_d"])
     lams = lams_of(a)
+    if a.fused_loss:
+        harness.FUSED_LOSS = True
     args_rec = {k: v for k, v in vars(a).items()}
 
     # the stage, resolved once: its sampler, its step (-> g_loss, d_loss or None), how its train PSNRs are read from the
@@ -339,7 +344,7 @@ def _train(a, dev, rank: int, world: int) -> dict:
     head = {"event": "start", "stage": a.stage, "g_step": g_step, "iterations": a.iterations, "rgb_frames": bank.n_rgb, "op_frames": bank.n_op,
             "sub_videos": len(bank.videos), "bank_GB": round(bank.nbytes / 1e9, 3), "fill_seconds": round(bank.fill_seconds, 3),
             "workers": a.workers, "batch": a.batch, "world": world, "global_batch": world * a.batch, "size": a.size,
-            "precision": a.precision, "sync_stats": bool(a.sync_stats and world > 1),
+            "precision": a.precision, "fused_loss": bool(harness.FUSED_LOSS), "sync_stats": bool(a.sync_stats and world > 1),
             "flow_term": ("off: no --flownet" if flow_fn is None else f"on ({a.flownet})"), "resumed": resumed is not None}
     log_path = os.path.join(a.out, "train_log.jsonl")
 

@@ -602,6 +602,33 @@ int ammc_codebook_ema_f32(const float* x, const int32_t* idx_topk, int32_t k, in
                           float decay, float one_minus_decay, float eps, float* cluster_size, float* embed_avg,
                           float* embed, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The per-pixel terms of the generator's objective and their gradient (csrc/loss.hip), on the NCHW fp32 tensors of the
+ * module boundary: pred / target [batch][c][h][w], c = 2 or 3 (otherwise AMMC_EUNSUP), dense, any h, w >= 1 (16-byte
+ * loads when w % 4 == 0 and the tensors start on 16-byte boundaries, 4-byte loads otherwise); the target's samples may lie target_bs >= c h w floats apart (the last frame of every clip of a batch, in place).  Replaces models/losses/losses_utils.py: `L2` (:124-129, the intensity term), `Gradient_Loss` (:30-61,
+ * alpha = 1 only) and `Flow_Loss` (:10-15).  No allocation, no synchronisation, no atomics; the same bits on every
+ * launch.  (The LSGAN terms, :100-110, act on patch maps of a few thousand elements and are not here.)
+ * ---------------------------------------------------------------------------------------- */
+#define AMMC_PRED_LOSS_ROWS 4  /* image rows one workgroup (= one partial row) of the two kernels below covers */
+#define AMMC_L1_CHUNK 4096     /* elements one workgroup (= one partial) of ammc_l1_partials_f32 covers         */
+/* partial rows of ammc_pred_loss_fwd_f32: ceil(batch * h / AMMC_PRED_LOSS_ROWS); 0 for a non-positive / oversized shape */
+int ammc_pred_loss_partial_rows(int32_t batch, int32_t h, int32_t w);
+/* partial[rows][2] = fp32 sums over the pixels of a workgroup's image rows (at most AMMC_PRED_LOSS_ROWS * w of them) of
+ *   [0] sqrt(sum_c (pred - target)^2)                      `torch.norm(pred - target, p=2, dim=1)` before the mean
+ *   [1] |tx - gx| + |ty - gy|  (want_gdl != 0, else 0)      s = sum_c, gx[x] = s[x] - s[x-1], gx[0] = s[0]; gy down the rows
+ * Combine with ammc_reduce_partials_f32(partial, rows, 2, 1 / (batch h w), out): out[0] = the intensity term, out[1] = the
+ * gradient-difference term (fp64, fixed order). */
+int ammc_pred_loss_fwd_f32(const float* pred, const float* target, int64_t target_bs, int32_t batch, int32_t c, int32_t h,
+                           int32_t w, int32_t want_gdl, float* partial, void* stream);
+/* d_pred (fully overwritten) = g_int[0] * d(intensity term) / d(pred) + g_gdl[0] * d(gradient-difference term) / d(pred);
+ * g_int / g_gdl: DEVICE scalars, either may be NULL (= 0; with g_gdl NULL no neighbour row is read).  torch's backward:
+ * 0 where the channel norm is 0, sign(0) = 0.  Reads rows y - 1, y, y + 1 of both tensors; nothing is materialised. */
+int ammc_pred_loss_bwd_f32(const float* pred, const float* target, int64_t target_bs, const float* g_int, const float* g_gdl,
+                           int32_t batch, int32_t c, int32_t h, int32_t w, float* d_pred, void* stream);
+/* partial[ceil(count / AMMC_L1_CHUNK)] = sums of |a - b| (value only: `Flow_Loss` on flows that carry no gradient);
+ * combine with ammc_sum_partials_f32(partial, n, 1 / count, out). */
+int ammc_l1_partials_f32(const float* a, const float* b, int64_t count, float* partial, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
