@@ -755,6 +755,13 @@ __global__ __launch_bounds__(256) void commit_bwd_kernel(const float* __restrict
 // synchronised three times per 256 rows and took 1.8 ms per launch).  Round 4: 16 waves per slot instead of 4 - the scan
 // of 32768 row indices by four waves was 240 us per launch with 256 workgroups of 256 threads on 256 CUs.
 constexpr int EMA_NW = 16;
+// The EMA blend decay * old + omd * val with its roundings spelled out: the product omd * val rounded, then one fused
+// multiply-add.  Left to the compiler's contraction, the fused kernel and ema_apply_kernel (the data-parallel form)
+// fused different products into the sum and differed by up to 69 ulp where the two terms cancel
+// (tests/test_gpu_stream_kernels.py::test_codebook_ema_fused_and_raw); now the two forms agree bit for bit.
+__device__ __forceinline__ float ema_blend(float decay, float old, float omd, float val) {
+  return __fmaf_rn(decay, old, __fmul_rn(omd, val));
+}
 __global__ __launch_bounds__(64 * EMA_NW) void ema_accumulate_kernel(const float* __restrict__ x, const int* __restrict__ idx,
                                                              int k, int N, int D, int M, float decay, float omd,
                                                              float* __restrict__ cluster_size,
@@ -821,10 +828,10 @@ __global__ __launch_bounds__(64 * EMA_NW) void ema_accumulate_kernel(const float
     if (threadIdx.x < D) embed_avg[(int64_t)threadIdx.x * M + slot] = sum;
     return;
   }
-  if (threadIdx.x == 0) cluster_size[slot] = decay * cluster_size[slot] + omd * (float)count;
+  if (threadIdx.x == 0) cluster_size[slot] = ema_blend(decay, cluster_size[slot], omd, (float)count);
   for (int d = threadIdx.x; d < D; d += 256) {
     // note: with D > 256 the loop above accumulates several features into one `sum`; guarded on the host (D <= 256)
-    embed_avg[(int64_t)d * M + slot] = decay * embed_avg[(int64_t)d * M + slot] + omd * sum;
+    embed_avg[(int64_t)d * M + slot] = ema_blend(decay, embed_avg[(int64_t)d * M + slot], omd, sum);
   }
 }
 
@@ -833,8 +840,8 @@ __global__ __launch_bounds__(256) void ema_apply_kernel(const float* __restrict_
                                                         int D, int M, float decay, float omd,
                                                         float* __restrict__ cluster_size, float* __restrict__ embed_avg) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < M) cluster_size[i] = decay * cluster_size[i] + omd * counts[i];
-  if (i < (int64_t)D * M) embed_avg[i] = decay * embed_avg[i] + omd * sums[i];
+  if (i < M) cluster_size[i] = ema_blend(decay, cluster_size[i], omd, counts[i]);
+  if (i < (int64_t)D * M) embed_avg[i] = ema_blend(decay, embed_avg[i], omd, sums[i]);
 }
 
 // step 2: n = sum(cluster_size); embed = embed_avg / ((cs + eps) / (n + M eps) * n)
