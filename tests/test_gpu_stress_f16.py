@@ -12,8 +12,19 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+@pytest.fixture
+def rows_in_registers(request):
+    """which of the two kernels `ops.quantize_topk_f16` launches: True = memory_topk_f16r.hip (the default), False =
+    memory_topk_f16.hip; restored afterwards"""
+    saved = ops.F16_ROWS_IN_REGISTERS
+    ops.F16_ROWS_IN_REGISTERS = request.param
+    yield request.param
+    ops.F16_ROWS_IN_REGISTERS = saved
+
+
+@pytest.mark.parametrize("rows_in_registers", [True, False], indirect=True, ids=["f16r", "f16"])
 @pytest.mark.parametrize("d,m,k,n", [(512, 8192, 2, 1024), (512, 8192, 2, 300), (128, 1000, 3, 513), (256, 4096, 1, 256)])
-def test_memory_topk_f16(d, m, k, n):
+def test_memory_topk_f16(d, m, k, n, rows_in_registers):
     embed = S.hashed_normal(f"s16:{d}:{m}", (d, m), 0.9)
     x = S.hashed_normal(f"s16x:{d}:{m}", (1, 1, n, d), 0.8)
     qk, diff, q1, idx = ops.quantize_topk_f16(embed.to(DEV), x.to(DEV), k)
@@ -98,8 +109,10 @@ def test_memory_topk_f16_65536_rows_chunked_oracle():
 
 
 @pytest.mark.parametrize("n", [65536, 65536 + 128 * 300 + 57, 1024])
-def test_split_contraction_and_gather_equal_the_fused_launch(n):
-    """`memory_split`: contraction in chunks of whole rounds on the caller's stream, gather / commit of every chunk on
+def test_split_contraction_and_gather_equal_the_fused_launch(n, monkeypatch):
+    """(runs memory_topk_f16.hip, the only kernel that reads `memory_split`: `ops.F16_ROWS_IN_REGISTERS` is False for its
+    duration - with the default the two modes both ran memory_topk_f16r.hip and the comparison was vacuous)
+    `memory_split`: contraction in chunks of whole rounds on the caller's stream, gather / commit of every chunk on
     the library's second stream beside the next chunk's contraction (the default from two rounds of workgroups up).  Same
     indices, same gathered fp32 rows and q_one bit for bit as ONE fused launch; the commit sum to summation order.  The
     ragged size ends in a partial chunk and a partial row block; 1024 rows force the split form below its default size.
@@ -107,6 +120,7 @@ def test_split_contraction_and_gather_equal_the_fused_launch(n):
     synchronisation in between."""
     from ammcnet_aaai2021_amd import _lib
     lib = _lib.load()
+    monkeypatch.setattr(ops, "F16_ROWS_IN_REGISTERS", False)
     d, m, k = 512, 8192, 2
     embed = S.hashed_normal("s16:split:e", (d, m), 0.9).to(DEV)
     g = torch.Generator().manual_seed(n)
