@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AMMC_LIB: another build of the SAME library (A/B measurements: `python -m ammcnet_aaai2021_amd.build --variant x`)
 LIB_PATH = os.environ.get("AMMC_LIB") or os.path.join(HERE, "libammc_hip.so")
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_LRELU = 0, 1, 2, 3
 
@@ -133,6 +133,7 @@ SIGNATURES = {
     "ammc_flows_resize_c0": (C.c_int, [_p, _i32, _i32, _i32, _p, _i32, _i32, _p]),
     "ammc_gather_clips": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "ammc_gather_clips_one": (C.c_int, [_p, _i64, _i32, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "ammc_gather_clips_tiered": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "ammc_bucket_pack_f32": (C.c_int, [C.POINTER(AmmcBucketTable), _i32, _i32, _p, _p]),
     "ammc_bucket_unpack_scale_f32": (C.c_int, [C.POINTER(AmmcBucketTable), _i32, _i32, _p, _f32, _p]),
     "ammc_chan_reduce_blocks": (C.c_int, [_i32]),

@@ -308,6 +308,41 @@ def bank_bytes(n_rgb_frames: int, n_op_frames: int, size) -> int:
     return n_rgb_frames * 3 * h * w + n_op_frames * 4 * h * w
 
 
+def bank_tiers(n_rgb: int, n_op: int, size, device_bytes: float, host_bytes: float) -> Tuple[int, int]:
+    """(n_rgb_dev, n_op_dev): how many leading frames of each kind of a two-tier ClipBank live in device memory, the
+    rest in pinned host memory.  Both kinds keep the same fraction on the device (a clip of either kind is then as likely
+    to come from the host tier), and the split is the largest that fits: the proportional share rounded down, then
+    single frames added - to the kind whose device fraction is the lower - while one still fits `device_bytes`.
+    Raises AmmcHipError when what is left over exceeds `host_bytes`."""
+    w, h = _size_wh(size)
+    cost = {"rgb": 3 * h * w, "op": 4 * h * w}
+    total = {"rgb": int(n_rgb), "op": int(n_op)}
+    all_bytes = bank_bytes(n_rgb, n_op, size)
+    if all_bytes <= device_bytes:
+        return total["rgb"], total["op"]
+    frac = max(0.0, float(device_bytes)) / all_bytes
+    dev = {k: min(total[k], int(total[k] * frac)) for k in total}
+    used = sum(dev[k] * cost[k] for k in dev)
+    while used > device_bytes:                                # (float rounding of the share: never more than a frame)
+        k = max(dev, key=lambda k: dev[k])
+        dev[k] -= 1
+        used -= cost[k]
+    while True:
+        open_ = sorted((k for k in dev if dev[k] < total[k] and used + cost[k] <= device_bytes),
+                       key=lambda k: dev[k] / total[k])
+        if not open_:
+            break
+        dev[open_[0]] += 1
+        used += cost[open_[0]]
+    rest = all_bytes - used
+    if rest > host_bytes:
+        raise _lib.AmmcHipError(
+            f"ClipBank: {n_rgb} frames + {n_op} flows at {w}x{h} need {all_bytes / 1e9:.2f} GB; {used / 1e9:.2f} GB fit the "
+            f"device budget of {device_bytes / 1e9:.2f} GB and the remaining {rest / 1e9:.2f} GB exceed the host budget of "
+            f"{host_bytes / 1e9:.2f} GB")
+    return dev["rgb"], dev["op"]
+
+
 class ClipBank:
     """Every frame of a training set, decoded once and resized once into device memory; each iteration's clips gathered
     from it by one launch (`csrc/clip_bank.hip`), bit-identical to `frames_to_device` / `flows_to_device`.
@@ -328,10 +363,24 @@ class ClipBank:
     One kind (a single-stream training stage): `rgb_root=None` or `op_root=None`.  Such a bank decodes, uploads and
     budgets only its kind (the other bank is None), `global_index(vid, start)` and `gather(first)` take and return that
     kind alone, and the gather is one launch of `ammc_gather_clips_one`, bit-identical to the matching half of the
-    two-kind gather.  `kinds`: ("rgb", "op"), ("rgb",) or ("op",)."""
+    two-kind gather.  `kinds`: ("rgb", "op"), ("rgb",) or ("op",).
+
+    Two tiers: with `host_budget_gb` > 0 a set that exceeds the device budget is not refused; `bank_tiers` keeps the
+    leading `n_rgb_dev` / `n_op_dev` frames in device memory (`rgb`, `op`) and the rest goes to ONE pinned host tensor
+    per kind (`rgb_host`, `op_host`), both tiers budgeted before anything is decoded.  A sub-video that reaches the host
+    tier is resized on the device into a bounce buffer (sized for the largest sub-video, released after the fill) and
+    copied from there into its slices on the fill stream; it may straddle the split.  Indices stay global, and the gather
+    is one launch of `ammc_gather_clips_tiered`, which reads the host tier through the host link and is bit-identical
+    to the all-device gather.  `device_nbytes` / `host_nbytes` (`nbytes` stays their sum); with `host_budget_gb=0`, or
+    when everything fits the device, nothing changes: no host tier, the same two kernels.
+
+    `prefetch(*first)` enqueues a gather on a stream the bank owns, behind everything already enqueued on the current
+    stream; the next `gather` with the same indices hands out its tensors (the current stream waits on the prefetch's
+    event, the host does not); a `gather` with other indices drops it."""
 
     def __init__(self, rgb_root: Optional[str], op_root: Optional[str], size, device, workers: int = 8,
-                 budget_gb: Optional[float] = None, rgb_len: int = 5, op_len: int = 4, bgr: bool = False):
+                 budget_gb: Optional[float] = None, rgb_len: int = 5, op_len: int = 4, bgr: bool = False,
+                 host_budget_gb: float = 0.0):
         import time
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -357,20 +406,38 @@ class ClipBank:
             budget, whose = 0.8 * free, f"80 % of the {free / 1e9:.2f} GB free on {self.device}"
         else:
             budget, whose = float(budget_gb) * 1e9, f"the budget of {float(budget_gb):.2f} GB"
-        if self.nbytes > budget:
+        self.n_rgb_dev, self.n_op_dev = self.n_rgb, self.n_op
+        if self.nbytes > budget and float(host_budget_gb) > 0:
+            self.n_rgb_dev, self.n_op_dev = bank_tiers(self.n_rgb, self.n_op, (self.width, self.height), budget,
+                                                       float(host_budget_gb) * 1e9)
+        elif self.nbytes > budget:
             raise _lib.AmmcHipError(
                 f"ClipBank: {self.n_rgb} frames + {self.n_op} flows at {self.width}x{self.height} need "
                 f"{self.nbytes / 1e9:.2f} GB of device memory, more than {whose}")
         if max(self.n_rgb, self.n_op) >= 2**31:
             raise _lib.AmmcHipError("ClipBank: more than 2^31 frames (the gather's indices are int32)")
+        self.device_nbytes = bank_bytes(self.n_rgb_dev, self.n_op_dev, (self.width, self.height))
+        self.host_nbytes = self.nbytes - self.device_nbytes
         t0 = time.perf_counter()
-        self.rgb = self.op = None
-        if "rgb" in self.kinds:
-            self.rgb = torch.empty(self.n_rgb, 3, self.height, self.width, dtype=torch.uint8, device=self.device)
-        if "op" in self.kinds:
-            self.op = torch.empty(max(self.n_op, 1), self.height, self.width, dtype=torch.float32, device=self.device)
+        self.rgb = self.op = self.rgb_host = self.op_host = None
+        if self.host_nbytes == 0:
+            if "rgb" in self.kinds:
+                self.rgb = torch.empty(self.n_rgb, 3, self.height, self.width, dtype=torch.uint8, device=self.device)
+            if "op" in self.kinds:
+                self.op = torch.empty(max(self.n_op, 1), self.height, self.width, dtype=torch.float32, device=self.device)
+        else:
+            if "rgb" in self.kinds:
+                self.rgb = torch.empty(self.n_rgb_dev, 3, self.height, self.width, dtype=torch.uint8, device=self.device)
+                self.rgb_host = torch.empty(self.n_rgb - self.n_rgb_dev, 3, self.height, self.width, dtype=torch.uint8,
+                                            pin_memory=True)
+            if "op" in self.kinds:
+                self.op = torch.empty(self.n_op_dev, self.height, self.width, dtype=torch.float32, device=self.device)
+                self.op_host = torch.empty(self.n_op - self.n_op_dev, self.height, self.width, dtype=torch.float32,
+                                           pin_memory=True)
         self._fill()
         self.fill_seconds = time.perf_counter() - t0
+        self._prefetch_stream = None                          # made by the first `prefetch`
+        self._prefetched = None                               # (index rows, output tensors, event)
         self._idx_pinned = [torch.empty(0, dtype=torch.int32).pin_memory() for _ in range(2)]
         self._idx_events = [None, None]
         self._idx_turn = 0
@@ -401,6 +468,31 @@ class ClipBank:
             staging[(kind, slot)] = (staging[(kind, slot)][0], ev)
             return dev
 
+        # the resize's destination: the sub-video's slice of the device tier, or - for a sub-video that reaches the host
+        # tier - a device bounce buffer whose parts then go to their tiers (`settle`), all in the fill stream's order
+        n_dev = {"rgb": self.n_rgb_dev, "op": self.n_op_dev}
+        tiers = {"rgb": (self.rgb, self.rgb_host), "op": (self.op, self.op_host)}
+        bounce = {}
+        for kind, starts, counts in (("rgb", self.rgb_start, self.rgb_count), ("op", self.op_start, self.op_count)):
+            reach = counts[starts + counts > n_dev[kind]] if self.host_nbytes and kind in self.kinds else []
+            if len(reach):
+                bounce[kind] = torch.empty(int(max(reach)), *tiers[kind][0].shape[1:], dtype=tiers[kind][0].dtype,
+                                           device=self.device)
+
+        def dest(kind, s0, cnt):
+            return tiers[kind][0][s0] if s0 + cnt <= n_dev[kind] else bounce[kind]
+
+        def settle(kind, s0, cnt):
+            split = n_dev[kind]
+            if s0 + cnt <= split:
+                return
+            dev, host = tiers[kind]
+            k = max(0, split - s0)                            # leading frames of the sub-video that stay on the device
+            with torch.cuda.stream(stream):
+                if k:
+                    dev[s0:split].copy_(bounce[kind][:k], non_blocking=True)
+                host[s0 + k - split:s0 + cnt - split].copy_(bounce[kind][k:cnt], non_blocking=True)
+
         with ThreadPoolExecutor(self.workers) as pool:
             for v, (frames, flows) in enumerate(self.videos):
                 slot = v % 2
@@ -416,10 +508,12 @@ class ClipBank:
                     dev = upload("rgb", slot, host)
                     s0 = int(self.rgb_start[v])
                     with torch.cuda.stream(stream):
-                        _lib.check(lib.ammc_frames_u8_resize_u8(dev.data_ptr(), len(imgs), h, w, self.rgb[s0].data_ptr(),
+                        _lib.check(lib.ammc_frames_u8_resize_u8(dev.data_ptr(), len(imgs), h, w,
+                                                                dest("rgb", s0, len(imgs)).data_ptr(),
                                                                 self.height, self.width, int(self.bgr), stream.cuda_stream),
                                    "frames_u8_resize_u8")
                         dev.record_stream(stream)
+                    settle("rgb", s0, len(imgs))
                 if flows:
                     fls = list(pool.map(_read_flow_file, flows))
                     h, w = fls[0].shape[:2]
@@ -432,11 +526,14 @@ class ClipBank:
                     dev = upload("op", slot, host)
                     s0 = int(self.op_start[v])
                     with torch.cuda.stream(stream):
-                        _lib.check(lib.ammc_flows_resize_c0(dev.data_ptr(), len(fls), h, w, self.op[s0].data_ptr(),
+                        _lib.check(lib.ammc_flows_resize_c0(dev.data_ptr(), len(fls), h, w,
+                                                            dest("op", s0, len(fls)).data_ptr(),
                                                             self.height, self.width, stream.cuda_stream), "flows_resize_c0")
                         dev.record_stream(stream)
+                    settle("op", s0, len(fls))
         stream.synchronize()
         torch.cuda.current_stream(self.device).wait_stream(stream)
+        bounce.clear()                                        # the fill is over (synchronised): the buffers go back
 
     # -- gather --------------------------------------------------------------------------------------------------------
 
@@ -486,14 +583,76 @@ class ClipBank:
         self._idx_events[k] = ev
         return idx
 
+    def _checked(self, first) -> Tuple[np.ndarray, ...]:
+        """the validated int64 index rows of a gather: (rgb, op), or the one row of a one-kind bank"""
+        one = self._single()
+        if one is None:
+            return self.validate(*first)
+        if len(first) != 1:
+            raise TypeError(f"ClipBank.gather: a {one}-only bank takes one index array, got {len(first)}")
+        first = first[0]
+        starts, counts, clip = (self.rgb_start, self.rgb_count, self.rgb_len) if one == "rgb" else \
+            (self.op_start, self.op_count, self.op_len)
+        f = check_clip_indices(one, first, starts, counts, clip)
+        if f.size == 0:
+            raise _lib.AmmcHipError("ClipBank.gather: need >= 1 index")
+        return (f,)
+
+    def _gather_tiered(self, rows):
+        """one launch of `ammc_gather_clips_tiered` on the current stream; returns what `gather` returns"""
+        one = self._single()
+        b = rows[0].size
+        idx = self._indices_to_device(rows)
+        stream = torch.cuda.current_stream(self.device)
+        rgb = op = None
+        if one != "op":
+            rgb = torch.empty(b, self.rgb_len, 3, self.height, self.width, dtype=torch.float32, device=self.device)
+        if one != "rgb":
+            op = torch.empty(b, self.op_len, 2, self.height, self.width, dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        _lib.check(_lib.load().ammc_gather_clips_tiered(
+            ptr(self.rgb), ptr(self.rgb_host), self.n_rgb_dev, self.n_rgb, ptr(self.op), ptr(self.op_host), self.n_op_dev,
+            self.n_op, idx[0].data_ptr() if rgb is not None else None, idx[-1].data_ptr() if op is not None else None, b,
+            self.rgb_len, self.op_len, self.height, self.width, ptr(rgb), ptr(op), stream.cuda_stream), "gather_clips_tiered")
+        return (rgb, op) if one is None else (rgb if one == "rgb" else op)
+
+    def _gather_rows(self, rows):
+        if self.host_nbytes:
+            return self._gather_tiered(rows)
+        return self._gather_one(self._single(), rows[0]) if self._single() is not None else self._gather_two(*rows)
+
+    def prefetch(self, *first) -> None:
+        """Enqueue the gather of `first` (as `gather` takes them, validated here) on the bank's own stream, which first
+        waits for everything already enqueued on the current stream, and record an event behind it.  The next `gather`
+        with the same indices returns these tensors.  They are fresh tensors of the bank's stream, handed to the
+        consumer's stream with `record_stream`: nothing a consumer may still read is ever rewritten."""
+        rows = self._checked(first)
+        if self._prefetch_stream is None:
+            self._prefetch_stream = torch.cuda.Stream(self.device)
+        side = self._prefetch_stream
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            out = self._gather_rows(rows)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        self._prefetched = (rows, out, ev)
+
     def gather(self, *first):
         """host int arrays of global first frames -> (rgb float32 [B, rgb_len, 3, H, W], op float32 [B, op_len, 2, H, W])
         on the current stream: the indices go H2D through one of two pinned buffers (event-guarded), then one launch.
-        A one-kind bank: `gather(first)` -> that kind's clips alone (`ammc_gather_clips_one`)."""
-        one = self._single()
-        if one is not None:
-            return self._gather_one(one, *first)
-        rf, of = self.validate(*first)
+        A one-kind bank: `gather(first)` -> that kind's clips alone (`ammc_gather_clips_one`).  After a `prefetch` of
+        the same indices: its tensors, once the current stream has waited on its event."""
+        rows = self._checked(first)
+        pre, self._prefetched = self._prefetched, None
+        if pre is not None and len(pre[0]) == len(rows) and all(np.array_equal(a, b) for a, b in zip(pre[0], rows)):
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(pre[2])
+            for t in (pre[1] if isinstance(pre[1], tuple) else (pre[1],)):
+                t.record_stream(cur)
+            return pre[1]
+        return self._gather_rows(rows)
+
+    def _gather_two(self, rf, of):
         b = rf.size
         idx = self._indices_to_device((rf, of))
         stream = torch.cuda.current_stream(self.device)
@@ -505,13 +664,9 @@ class ClipBank:
                    "gather_clips")
         return rgb, op
 
-    def _gather_one(self, kind: str, first) -> torch.Tensor:
+    def _gather_one(self, kind: str, f: np.ndarray) -> torch.Tensor:
         rgb = kind == "rgb"
-        starts, counts = (self.rgb_start, self.rgb_count) if rgb else (self.op_start, self.op_count)
         clip, n, bank = (self.rgb_len, self.n_rgb, self.rgb) if rgb else (self.op_len, self.n_op, self.op)
-        f = check_clip_indices(kind, first, starts, counts, clip)
-        if f.size == 0:
-            raise _lib.AmmcHipError("ClipBank.gather: need >= 1 index")
         idx = self._indices_to_device((f,))
         stream = torch.cuda.current_stream(self.device)
         out = torch.empty(f.size, clip, 3 if rgb else 2, self.height, self.width, dtype=torch.float32, device=self.device)

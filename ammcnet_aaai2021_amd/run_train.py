@@ -42,6 +42,15 @@ Several GPUs: one process per GPU under `torchrun` (or plain RANK / LOCAL_RANK /
     and a run may be resumed with another world as long as `world x batch` is unchanged (anything else is refused).
   * Every rank fills its own FULL `ClipBank` (ShanghaiTech at 256 x 256 is ~126 GB: it fits one MI355X); `--workers` is
     per rank.  A bank sharded over the ranks is the follow-up, not part of this entry.
+  * `--bank_host_gb G` (default 0: off) lets a set larger than the device budget train: what `--bank_budget_gb` does not
+    hold goes to a second tier of the bank in pinned host memory, up to G GB (`pipeline.bank_tiers`; one gather launch
+    reads both tiers, bit-identical to the all-device gather).  With a host tier the loop prefetches: iteration i takes
+    its clips, draws iteration i + 1's indices from the one sampler stream (the same order as without), enqueues their
+    gather on the bank's side stream (`ClipBank.prefetch`) and then launches its step.  Measured: a
+    bank entirely in host memory costs 1.2 ms per iteration at batch 32, 256 x 256, and the prefetch does not hide it
+    yet.  The train state is the same (the sampler state before the draw of the first iteration a resume
+    runs), so --resume and the world x batch rule hold unchanged.  EVERY rank pins its own full host tier: N ranks on
+    one host cost N x G GB of pinned host memory; sharing the tier between the ranks is not part of this entry.
   * The models are built and seeded alike on every rank and then broadcast from rank 0 (`parallel.broadcast_state`);
     gradients are averaged by one `parallel.BucketedGradReducer` per network, fed stage by stage by the backward.
     BatchNorm and EMA-codebook statistics stay per rank (stock DDP semantics, see parallel.py) unless `--sync_stats`
@@ -104,6 +113,9 @@ def parse(argv=None) -> argparse.Namespace:
     p.add_argument("--seed", type=int, default=2017, help="sampler RandomState seed (the reference's 2017) and torch seed")
     p.add_argument("--workers", type=int, default=8, help="decoder threads of the bank fill (per rank)")
     p.add_argument("--bank_budget_gb", type=float, default=None, help="default: 80%% of the free device memory")
+    p.add_argument("--bank_host_gb", type=float, default=0.0,
+                   help="pinned host memory (GB, per rank) for the frames the device budget does not hold; 0 = none: a "
+                        "set over the device budget is refused")
     p.add_argument("--log_every", type=int, default=10)
     p.add_argument("--save_every", type=int, default=1000)
     p.add_argument("--resume", action="store_true")
@@ -134,6 +146,8 @@ def parse(argv=None) -> argparse.Namespace:
         p.error("--flownet: the flow term belongs to the rgb and joint stages")
     if (a.pretrain_rgb is None) != (a.pretrain_op is None):
         p.error("--pretrain_rgb and --pretrain_op go together")
+    if a.bank_host_gb < 0:
+        p.error("--bank_host_gb must be >= 0")
     if a.iterations <= 0 or a.batch <= 0 or a.log_every <= 0 or a.save_every <= 0:
         p.error("--iterations, --batch, --log_every and --save_every must be positive")
     return a
@@ -269,7 +283,8 @@ def _train(a, dev, rank: int, world: int) -> dict:
     os.makedirs(a.out, exist_ok=True)
 
     bank = pipeline.ClipBank(a.rgb_root, a.op_root, a.size, dev, workers=a.workers, budget_gb=a.bank_budget_gb,
-                             rgb_len=harness.RGB_LEN_CLIP, op_len=harness.OP_LEN_CLIP)
+                             rgb_len=harness.RGB_LEN_CLIP, op_len=harness.OP_LEN_CLIP, host_budget_gb=a.bank_host_gb)
+    prefetch = bank.host_nbytes > 0                 # exactly when there is a host tier: the all-device loop is untouched
     G, D, F2 = build_models(a)
     g_step, resumed = 0, None
     if a.resume:
@@ -342,7 +357,8 @@ def _train(a, dev, rank: int, world: int) -> dict:
         sampler.set_state(resumed["sampler"])
 
     head = {"event": "start", "stage": a.stage, "g_step": g_step, "iterations": a.iterations, "rgb_frames": bank.n_rgb, "op_frames": bank.n_op,
-            "sub_videos": len(bank.videos), "bank_GB": round(bank.nbytes / 1e9, 3), "fill_seconds": round(bank.fill_seconds, 3),
+            "sub_videos": len(bank.videos), "bank_GB": round(bank.nbytes / 1e9, 3),
+            "bank_device_GB": round(bank.device_nbytes / 1e9, 6), "bank_host_GB": round(bank.host_nbytes / 1e9, 6), "prefetch": prefetch, "fill_seconds": round(bank.fill_seconds, 3),
             "workers": a.workers, "batch": a.batch, "world": world, "global_batch": world * a.batch, "size": a.size,
             "precision": a.precision, "fused_loss": bool(harness.FUSED_LOSS), "sync_stats": bool(a.sync_stats and world > 1),
             "flow_term": ("off: no --flownet" if flow_fn is None else f"on ({a.flownet})"), "resumed": resumed is not None}
@@ -374,6 +390,13 @@ def _train(a, dev, rank: int, world: int) -> dict:
         log_now = g_step % a.log_every == 0 or g_step == a.iterations
         th = time.perf_counter()
         clips = bank.gather(*pending)               # joint: (rgb, op); a single stage: its clips
+        if prefetch:
+            # a host tier: iteration g_step + 1's clips are drawn NOW (the same stream, the same order) and their gather
+            # is enqueued on the bank's stream before this step is launched
+            state_before = sampler.get_state()
+            pending = draw()
+            if g_step < a.iterations:
+                bank.prefetch(*pending)
         host_data_s += time.perf_counter() - th
         outputs = {} if log_now else None
         try:
@@ -393,10 +416,11 @@ def _train(a, dev, rank: int, world: int) -> dict:
                 dist.all_reduce(vals)
                 vals /= world
         # iteration g_step + 1's clips are drawn while the device runs this one
-        th = time.perf_counter()
-        state_before = sampler.get_state()
-        pending = draw()
-        host_data_s += time.perf_counter() - th
+        if not prefetch:
+            th = time.perf_counter()
+            state_before = sampler.get_state()
+            pending = draw()
+            host_data_s += time.perf_counter() - th
         sched_g.step()
         if sched_d is not None:
             sched_d.step()

@@ -449,6 +449,24 @@ int ammc_gather_clips(const uint8_t* rgb_bank, int64_t n_rgb, const float* op_ba
 int ammc_gather_clips_one(const void* bank, int64_t n, int32_t kind, const int32_t* first, int32_t batch, int32_t len,
                           int32_t h, int32_t w, float* out, void* stream);
 
+/* The same gather from a bank split between two tiers (pipeline.ClipBank with a host budget), one launch: frames
+ * [0, n_*_dev) of a kind are device memory at *_dev + f * stride, frames [n_*_dev, n_*) are pinned or registered,
+ * device-mapped HOST memory at *_host + (f - n_*_dev) * stride (stride: 3 h w bytes of the rgb bank, h w floats of the
+ * op bank).  Output layout, normalisation, derived flow channel and the NaN rule are those of ammc_gather_clips, so the
+ * result is bit-identical to it (and to ammc_gather_clips_one) on an all-device copy of the bank wherever the split
+ * lies, a clip that straddles it included.  A kind whose `first` is NULL is skipped (its other arguments are not read):
+ * one entry for the joint stage and both single stages; both NULL is AMMC_EINVAL.
+ * Needs h * w % 4 == 0; 0 <= n_dev <= n and n >= len per kind; a tier's base may be NULL only if the tier is empty;
+ * rgb_dev 4-byte, op_dev, both host bases and the outputs 16-byte aligned; batch * planes <= 65535 (3 planes per rgb
+ * frame, one per op frame, of the kinds gathered).  The host tier is read 16 bytes per lane, several loads in flight
+ * (16 rgb pixels per load when h * w % 16 == 0, 4 otherwise).  A non-empty host tier whose base
+ * hipPointerGetAttributes does not report as host memory mapped to the device - a pageable pointer - is AMMC_EINVAL and
+ * nothing is launched; that check runs after all the others, which need no device. */
+int ammc_gather_clips_tiered(const uint8_t* rgb_dev, const uint8_t* rgb_host, int64_t n_rgb_dev, int64_t n_rgb,
+                             const float* op_dev, const float* op_host, int64_t n_op_dev, int64_t n_op,
+                             const int32_t* rgb_first, const int32_t* op_first, int32_t batch, int32_t rgb_len,
+                             int32_t op_len, int32_t h, int32_t w, float* rgb_out, float* op_out, void* stream);
+
 /* Gradient buckets of data-parallel training (parallel.BucketedGradReducer; the reference is single-GPU): the gather of
  * up to AMMC_BUCKET_MAX contiguous fp32 member tensors into one flat all-reduce buffer, and the way back with the
  * average folded in, one launch each (torch._foreach_copy_ / _foreach_mul_ / _foreach_copy_ otherwise).
