@@ -33,7 +33,10 @@ constexpr int O_APIECES = O_HP * 8;                                             
 constexpr int O_NT = 512;
 constexpr int O_R = (O_APIECES + O_NT - 1) / O_NT;                               // 6 DMA rounds per patch
 constexpr int O_ASTAGE = ((O_APIECES + 63) / 64) * 64 * 4;                       // floats: 43 KB (whole wave-instructions)
-constexpr int O_TG = 3 * 256;                                                    // target tile: <= 3 channels x 8 x 32 floats
+constexpr int O_MAXNS = 4;                                                     // <= 4 stored channels (conv_outc_s16_try)
+constexpr int O_TG = O_MAXNS * 256;                                              // target tile: <= 4 channels x 8 x 32 floats (at 3 x 256 the fourth
+                                                                                // channel of buffer 0 was buffer 1's first and that of buffer 1 lay in Scr:
+                                                                                // n_store = 4 with a target summed against the wrong tile)
 constexpr int O_NS = 3;                                                          // patch stages
 constexpr int O_MAXCC = 2;                                                       // <= 64 input channels (LDS: 144 + 9 KB)
 static_assert(O_R == 6, "OUTC_WAIT below knows 0, 2, 6 and 8 outstanding operations");
@@ -272,7 +275,7 @@ int conv_outc_s16_try(const AmmcConvDesc& d, int kpad, hipStream_t stream, char*
   constexpr int OUTC_SKIP = -12345;
   if (!(d.outc_stream ? d.outc_stream - 1 : ammc_opt_outc_stream())) return OUTC_SKIP;   // per call, else the process default
   const int ns = d.n_store > 0 ? d.n_store : d.n;
-  if (d.ntaps != 9 || d.up != 1 || d.x_step > 1 || !d.y_f32 || d.n != 32 || ns > 4 || d.res || d.pool_y) return OUTC_SKIP;
+  if (d.ntaps != 9 || d.up != 1 || d.x_step > 1 || !d.y_f32 || d.n != 32 || ns > O_MAXNS || d.res || d.pool_y) return OUTC_SKIP;
   if (d.cin % 32 || d.cin / 32 > O_MAXCC || d.width % O_TW || d.height % O_TH) return OUTC_SKIP;
   if (d.sq_target && !d.sq_acc) return AMMC_EINVAL;
   OutcArgs a;

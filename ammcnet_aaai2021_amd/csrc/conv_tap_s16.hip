@@ -1129,8 +1129,13 @@ int conv_tap_s16_try(const AmmcConvDesc& d, int kpad, hipStream_t stream, char* 
     const int rc = conv_outc_s16_try(d, kpad, stream, label, label_len);      // the streaming form (conv_outc_s16.hip)
     if (rc != TAP_SKIP) return rc;
   }
-  if (d.n == 32) return mf ? launch_tap<4, 1, 2, 1, 1, 1>(a, stream, label, label_len)
-                           : launch_tap<8, 1, 1, 1, 1, 0>(a, stream, label, label_len);
+  // (the 16x16x32 instance contracts ONE 16-filter MFMA tile and its epilogue stores filters 0 .. 3 of it - the output
+  // layer's 2-3 channels.  With more stored columns it left channels 4 .. 7, 12 .. 15, 20 .. 31 of every pixel unwritten
+  // (tests/test_gpu_patch_kernels.py: n_store = 5 and the fp32 NHWC store of all 32): those go to the 32x32x16 form, which
+  // holds the whole 32-filter tile, whatever s16_mf says)
+  const int ns32 = d.n_store > 0 ? d.n_store : d.n;
+  if (d.n == 32) return (mf && ns32 <= 4) ? launch_tap<4, 1, 2, 1, 1, 1>(a, stream, label, label_len)
+                                          : launch_tap<8, 1, 1, 1, 1, 0>(a, stream, label, label_len);
   // The 4-wave forms (two workgroups per CU) run the k-half-major software pipeline (KH, 32x32x16) by default
   // (AMMC_TAP_KH: 0 = the tap-by-tap loop everywhere, 1 = default, 2 = KH wherever it exists).  Measured per layer on
   // random operands at batch 16 (tools/conv_bench.py --net, one box, us; tap-by-tap 4-wave / KH / 8-wave 16x16x32):
