@@ -1085,15 +1085,12 @@ int conv_tap_s16_stat_rows(const AmmcConvDesc& d) { return d.batch * (d.height /
 // Called by ammc_conv_gemm_s16 (conv_gemm_s16.hip) after its argument checks.  Returns TAP_SKIP when the descriptor is
 // not this kernel's case (the caller then runs the implicit-GEMM kernel), else the launch status.
 int conv_tap_s16_try(const AmmcConvDesc& d, int kpad, hipStream_t stream, char* label, int label_len) {
-  static const int mode = getenv("AMMC_S16_TAP") ? atoi(getenv("AMMC_S16_TAP")) : 1;
   static const int dbg = getenv("AMMC_S16_DBG") ? atoi(getenv("AMMC_S16_DBG")) : 0;
   constexpr int TAP_SKIP = -12345;
-  if (!mode) return TAP_SKIP;
   if (d.ntaps != 9 || d.up != 1 || d.x_step > 1) return TAP_SKIP;
-  // (round 6: LeakyReLU(0.1) in the epilogues - FlowNet2-SD's stride-1 3x3 layers at 128x128 ... 32x32 take the halo-patch
-  // kernels; AMMC_TAP_LRELU=0 sends them back to the implicit GEMM for A/Bs)
-  static const int tap_lrelu = getenv("AMMC_TAP_LRELU") ? atoi(getenv("AMMC_TAP_LRELU")) : 1;
-  if (d.act == AMMC_ACT_LRELU && (!tap_lrelu || d.y_f32)) return TAP_SKIP;      // (the S16-output epilogues have it; fp32 outputs: the GEMM kernel)
+  // (round 6: LeakyReLU(0.1) in the S16-output epilogues - FlowNet2-SD's stride-1 3x3 layers at 128x128 ... 32x32 take
+  // the halo-patch kernels; fp32 outputs: the GEMM kernel)
+  if (d.act == AMMC_ACT_LRELU && d.y_f32) return TAP_SKIP;
   if (d.cin % 32 || d.width % T_TW || d.height % T_TH) return TAP_SKIP;
   if (d.n != 32 && d.n != 64 && d.n % 128) return TAP_SKIP;
   if (d.n == 32 && !d.y_f32) return TAP_SKIP;
@@ -1115,14 +1112,12 @@ int conv_tap_s16_try(const AmmcConvDesc& d, int kpad, hipStream_t stream, char* 
 #else
   a.stamps = nullptr;
 #endif
-  // the MFMA shape per variant (option "s16_mf": -1 = the measured faster one, 0 / 1 = forced for A/Bs).  Measured at
-  // batch 16, 256x256 on one MI355X: output layer 147 -> 123 us and 64-filter layers 306 -> 293 us
-  // with 16x16x32, 128-filter layers 213 -> 220 us (twice the MFMA instructions leave the fragment reads and the
-  // 2^-11 scaling half the issue slots), the 8-wave two-accumulator variant 165 -> 158 us
-  const int mfo = d.s16_mf ? d.s16_mf - 1 : ammc_opt_s16_mf();      // the call's own choice, else the process default
-  const int64_t ntiles = (int64_t)d.batch * (d.height / T_TH) * (d.width / T_TW) * (d.n <= 64 ? 1 : d.n / 128);
-  const bool wide4 = d.n > 64 && (mode == 4 || (mode == 1 && ntiles >= 512));          // the 4-wave 128-filter variant
-  const int mf = mfo < 0 ? (wide4 ? 0 : 1) : mfo;
+  // the MFMA shape (the call's own s16_mf, else the option "s16_mf"): -1 = the measured rule below, 0 = 32x32x16 and
+  // 1 = 16x16x32 forced, which take the tap-by-tap loops of round 2 (the k-half-major pipeline exists in 32x32x16 only and
+  // is what -1 picks).  Measured at batch 16, 256x256 on one MI355X: output layer 147 -> 123 us and
+  // 64-filter layers 306 -> 293 us with 16x16x32, 4-wave 128-filter layers 213 -> 220 us (twice the MFMA instructions
+  // leave the fragment reads and the 2^-11 scaling half the issue slots), the 8-wave two-accumulator variant 165 -> 158 us
+  const int mfo = d.s16_mf ? d.s16_mf - 1 : ammc_opt_s16_mf();
   // the output layer (2-3 filters, fp32 NCHW + tanh): 4 waves, 52 KB of LDS, THREE workgroups per CU (124 us against
   // 128 for the 8-wave form at two per CU; the layer waits for its 45-KB patches, not for the matrix pipe)
   if (d.n == 32 && !d.stats) {
@@ -1134,26 +1129,25 @@ int conv_tap_s16_try(const AmmcConvDesc& d, int kpad, hipStream_t stream, char* 
   // (tests/test_gpu_patch_kernels.py: n_store = 5 and the fp32 NHWC store of all 32): those go to the 32x32x16 form, which
   // holds the whole 32-filter tile, whatever s16_mf says)
   const int ns32 = d.n_store > 0 ? d.n_store : d.n;
-  if (d.n == 32) return (mf && ns32 <= 4) ? launch_tap<4, 1, 2, 1, 1, 1>(a, stream, label, label_len)
-                                          : launch_tap<8, 1, 1, 1, 1, 0>(a, stream, label, label_len);
-  // The 4-wave forms (two workgroups per CU) run the k-half-major software pipeline (KH, 32x32x16) by default
-  // (AMMC_TAP_KH: 0 = the tap-by-tap loop everywhere, 1 = default, 2 = KH wherever it exists).  Measured per layer on
-  // random operands at batch 16 (tools/conv_bench.py --net, one box, us; tap-by-tap 4-wave / KH / 8-wave 16x16x32):
-  // 128x128 64->128 113 / 109 / 125, 128->128 202 / 192 / 203, 256->128 366 / 354 / 354; 64x64 (512 tiles = ONE round
-  // of two workgroups per CU, nothing for a second workgroup to hide behind) 128->256 100 / 98 / 97.5, 256->256
-  // 185 / 181 / 170, 512->256 351 / 340 / 314: from two rounds up the 4-wave KH form, below that the 8-wave form.
-  static const int kh = getenv("AMMC_TAP_KH") ? atoi(getenv("AMMC_TAP_KH")) : 1;
-  if (d.n == 64 && kh && mfo < 0) return launch_tap<4, 1, 2, 2, 1, 0, 1>(a, stream, label, label_len);
-  if (d.n == 64) return mf ? launch_tap<4, 1, 2, 2, 1, 1>(a, stream, label, label_len)     // 4 waves of 64x64 (2 image rows x 64 filters), 2 workgroups per CU
-                           : launch_tap<4, 1, 2, 2, 1, 0>(a, stream, label, label_len);
-  // 4 waves of 64x128 (one accumulator set), two workgroups per CU: fewer LDS reads per MFMA and the neighbour's
-  // MFMAs behind every prologue / epilogue - once there are two workgroups for every CU
-  if (mfo < 0 && ((kh == 1 && mode == 1 && tiles >= 1024) || (kh == 2 && tiles >= 512) || (kh && mode == 4)))
-    return launch_tap<4, 1, 2, 4, 1, 0, 1>(a, stream, label, label_len);
-  if (mode == 4 || (mode == 1 && tiles >= 512 && (!kh || mfo >= 0)))
-    return mf ? launch_tap<4, 1, 2, 4, 1, 1>(a, stream, label, label_len) : launch_tap<4, 1, 2, 4, 1, 0>(a, stream, label, label_len);
-  if (mfo < 0) return launch_tap<4, 2, 2, 2, 2, 1>(a, stream, label, label_len);
-  return mf ? launch_tap<4, 2, 2, 2, 2, 1>(a, stream, label, label_len) : launch_tap<4, 2, 2, 2, 2, 0>(a, stream, label, label_len);
+  if (d.n == 32) return (mfo != 0 && ns32 <= 4) ? launch_tap<4, 1, 2, 1, 1, 1>(a, stream, label, label_len)
+                                                : launch_tap<8, 1, 1, 1, 1, 0>(a, stream, label, label_len);
+  // 64 filters: 4 waves of 64x64 (2 image rows x 64 filters), two workgroups per CU - on the k-half-major software
+  // pipeline (KH, 32x32x16) unless an MFMA shape is forced: the forced shapes take the tap-by-tap instances
+  if (d.n == 64) {
+    if (mfo < 0) return launch_tap<4, 1, 2, 2, 1, 0, 1>(a, stream, label, label_len);
+    return mfo ? launch_tap<4, 1, 2, 2, 1, 1>(a, stream, label, label_len) : launch_tap<4, 1, 2, 2, 1, 0>(a, stream, label, label_len);
+  }
+  // 128 filters and more.  The 4-wave form (64x128, one accumulator set, two workgroups per CU) has fewer LDS reads per
+  // MFMA and the neighbour's MFMAs behind every prologue / epilogue - once there are two workgroups for every CU.
+  // Measured per layer on random operands at batch 16 (tools/conv_bench.py --net, one box, us; tap-by-tap 4-wave / KH /
+  // 8-wave 16x16x32): 128x128 64->128 113 / 109 / 125, 128->128 202 / 192 / 203, 256->128 366 / 354 / 354; 64x64 (512
+  // tiles = ONE round of two workgroups per CU, nothing for a second workgroup to hide behind) 128->256 100 / 98 / 97.5,
+  // 256->256 185 / 181 / 170, 512->256 351 / 340 / 314: from two rounds up the 4-wave KH form, below that the 8-wave form.
+  if (mfo < 0) return tiles >= 1024 ? launch_tap<4, 1, 2, 4, 1, 0, 1>(a, stream, label, label_len)
+                                    : launch_tap<4, 2, 2, 2, 2, 1>(a, stream, label, label_len);
+  // a forced MFMA shape: the tap-by-tap 4-wave form from one round up, the 8-wave form below
+  if (tiles >= 512) return mfo ? launch_tap<4, 1, 2, 4, 1, 1>(a, stream, label, label_len) : launch_tap<4, 1, 2, 4, 1, 0>(a, stream, label, label_len);
+  return mfo ? launch_tap<4, 2, 2, 2, 2, 1>(a, stream, label, label_len) : launch_tap<4, 2, 2, 2, 2, 0>(a, stream, label, label_len);
 }
 
 }  // namespace ammc_s16

@@ -328,7 +328,7 @@ class _Builder:
         d = AmmcConvDesc()
         d.y_f32 = 1 if (y_f32 and self.s16) else 0
         d.overflow_flag = self.overflow.data_ptr() if self.s16 else None
-        if self.s16 and os.environ.get("AMMC_S16_SPLITK", "1") != "0":
+        if self.s16:                         # split-K workspace, for layers that cannot fill the chip
             ws = self.splitk
             if self.plan.lane in (1, 3):
                 if self.splitk_b is None:
@@ -409,16 +409,14 @@ class _Builder:
 
     def up_conv_eligible(self, skip: Act, n: int) -> bool:
         """does csrc/conv_up_s16.hip take this decoder level?  (mirrors the checks of `ammc_conv_up_s16`)"""
-        mode = os.environ.get("AMMC_UP_FUSED", "1")
-        if not (self.s16 and mode != "0" and skip.W % 32 == 0 and skip.H % 8 == 0 and skip.c % 32 == 0
+        if not (self.s16 and skip.W % 32 == 0 and skip.H % 8 == 0 and skip.c % 32 == 0
                 and (n == 64 or n % 128 == 0)):
             return False
         # one workgroup per 8 x 32 output tile and 128 filters: below ~128 of them the chip is empty and the two
         # launches it replaces (implicit GEMMs with split-K) win - measured at 256x256: batch 1, up1 (32 tiles) 203 us
         # against 74, up2 (64) 105 against 69; batch 2, up2 (128) 110 against 114; up3 (256 per clip) always ahead
-        # (AMMC_UP_FUSED=2 forces the fused kernel)
         tiles = skip.B * (skip.H // 8) * (skip.W // 32) * max(1, n // 128)
-        return tiles >= 128 or mode == "2"
+        return tiles >= 128
 
     def up_conv(self, x2: Act, skip: Act, p: _DoubleConvPack, fused, y: Act, name="up"):
         """ConvTranspose2d(x2) + cat([skip, .]) + conv3x3 + BN + ReLU as ONE launch (reference unet.py:50-59, first conv
@@ -486,8 +484,7 @@ class StreamGraph:
         pooled = bld.act(B, self.hs[1], self.ws[1], chans[0])
         # the first layer reads the NCHW input itself where csrc/conv_first_s16.hip applies (launched per forward by
         # EvalEngine._launch_all: the input pointer changes); else layout kernel + implicit GEMM
-        self.first_mid = mid if (bld.s16 and sp.first is not None and W % 32 == 0 and H % 8 == 0 and
-                                 os.environ.get("AMMC_FIRST_FUSED", "1") != "0") else None
+        self.first_mid = mid if (bld.s16 and sp.first is not None and W % 32 == 0 and H % 8 == 0) else None
         if self.first_mid is not None:
             p, si = sp.inc, self.index
 
@@ -527,7 +524,7 @@ class StreamGraph:
         self.diff = bld.buf(1)
         bld.plan.keep.extend([self.idx, v["embed"], v["e_md"], v["enorm"]])
         if (bld.s16 and v.get("e_s16") is not None and FUSED_MEMORY and (d, k) == (64, 2) and m <= 2048 and
-                self.x4.c == 512 and self.x4.c_off == 0 and os.environ.get("AMMC_MEMORY_S16", "1") != "0"):
+                self.x4.c == 512 and self.x4.c_off == 0):
             # round 6: the whole block as ONE launch (csrc/memory_topk_s16.hip, `memory_block_s16_kernel`): z, the n x m
             # distances, the gathered rows and their S16 re-encoding never leave the CU; bit-identical to the chain below
             self.x4q = bld.act(B, h, w, 512)
@@ -549,14 +546,14 @@ class StreamGraph:
         self.z = bld.act(B, h, w, d, halo=0)
         bld.conv(self.x4, v["enc_w"], self.z, ntaps=1, cin=512, n=d, shift=v["enc_b"], name="vq.enc", y_f32=True)
         self.qk = bld.act(B, h, w, k * d, halo=0)
-        if v.get("e_s16") is not None and os.environ.get("AMMC_MEMORY_S16", "1") != "0":
+        if v.get("e_s16") is not None:
             # S16 plans: the distance GEMM in fp32-equivalent split-fp16 arithmetic (csrc/memory_topk_s16.hip)
             bld.plan.keep.append(v["e_s16"])
             bld.plan.add(lib.ammc_memory_topk_fwd_s16, _ptr(self.z.buf), v["e_s16"].data_ptr(), _ptr(v["e_md"]),
                          _ptr(v["enorm"]), n, d, m, k, self.idx.data_ptr(), _ptr(self.qk.buf), _ptr(self.q_one),
                          _ptr(self.diff_part), name="vq.memory_topk", flops=2.0 * n * d * m,
                          nbytes=4.0 * (n * d + d * m + n * k * d + n * k + n * d), kernel="memory_topk_s16")
-        else:
+        else:            # fp32 plans, d != 64, and a codebook whose S16 image left the half range
             bld.plan.add(lib.ammc_memory_topk_fwd_f32, _ptr(self.z.buf), _ptr(v["embed"]), _ptr(v["e_md"]),
                          _ptr(v["enorm"]), n, d, m, k, self.idx.data_ptr(), _ptr(self.qk.buf), _ptr(self.q_one),
                          _ptr(self.diff_part), name="vq.memory_topk", flops=2.0 * n * d * m,

@@ -34,7 +34,7 @@ from .train import BlockEngine, BlockFunction, HipPathFunction, MemoryBlockEngin
 # device flag beyond it and the guard below (on by default, `model.s16_guard = False` turns it off) recomputes the
 # batch on the exact-fp32 kernels, so the default mode never returns frames computed from a saturated activation.
 DEFAULT_PRECISION = os.environ.get("AMMC_PRECISION", "s16")
-DEFAULT_S16_GUARD = os.environ.get("AMMC_S16_GUARD", "1") != "0"      # (A/B measurements of the guard's cost only)
+DEFAULT_S16_GUARD = True
 
 
 def _run_memory(mod, kind: str, x):

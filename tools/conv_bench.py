@@ -3,7 +3,7 @@
     python tools/conv_bench.py B H W CIN N [reps]          one shape
     python tools/conv_bench.py --net [B] [reps]            the 3x3 layer shapes of the 256x256 network at batch B (16)
 
-env: AMMC_S16_TAP=0 (GEMM kernel), AMMC_S16_DBG=2 (no MFMA) / 3 (no DMA in the loop; tap kernel only, -DAMMC_TAP_DEBUG),
+env: AMMC_S16_DBG=2 (no MFMA) / 3 (no DMA in the loop; tap kernel only, -DAMMC_TAP_DEBUG),
      AMMC_LIB=path of another build of the library (A/Bs inside one gpurun call)"""
 import ctypes as C
 import sys

@@ -150,7 +150,7 @@ if "--wgrad" in sys.argv:                                  # the 3x3 weight-grad
         run_case(f"wgrad {cin}->{n} @{Hh} b{B}", lambda s: lib.ammc_conv_wgrad_s16(C.byref(d), None, s), 2.0 * B * Hh * W * n * cin * 9)
         del A32, G32, A16, G16
     sys.exit(0)
-if "--variants" in sys.argv:                               # forced MFMA shapes; AMMC_TAP_KH from the environment
+if "--variants" in sys.argv:                               # forced MFMA shapes
     for shape in [(16, 128, 128, 128, 128), (16, 128, 128, 64, 128), (16, 256, 256, 64, 64), (16, 64, 64, 256, 256)]:
         for mf in (0, 1, 2):
             conv_case(*shape, mf=mf)
