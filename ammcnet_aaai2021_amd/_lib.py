@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 # AMMC_LIB: another build of the SAME library (A/B measurements: `python -m ammcnet_aaai2021_amd.build --variant x`)
 LIB_PATH = os.environ.get("AMMC_LIB") or os.path.join(HERE, "libammc_hip.so")
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_LRELU = 0, 1, 2, 3
 
@@ -112,6 +112,8 @@ SIGNATURES = {
     "ammc_memory_topk_fwd_f16r": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "ammc_conv_wgrad_f32": (C.c_int, [C.POINTER(AmmcWgradDesc), _p]),
     "ammc_conv_wgrad_s16": (C.c_int, [C.POINTER(AmmcWgradDesc), _p, _p]),
+    "ammc_conv_wgrad_s16_variant": (C.c_int, [C.POINTER(AmmcWgradDesc), C.c_char_p, _i32]),
+    "ammc_conv_wgrad_s16_slabs_variant": (C.c_int, [C.POINTER(AmmcWgradDesc), C.c_char_p, _i32]),
     "ammc_conv_wgrad_s16_slab_floats": (C.c_int64, [C.POINTER(AmmcWgradDesc)]),
     "ammc_conv_wgrad_s16_slabs": (C.c_int, [C.POINTER(AmmcWgradDesc), _p, _p, _i64, _p, _i32, _i32, _p]),
     "ammc_unpack_conv_wgrad_f32": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),

@@ -20,6 +20,7 @@
 // G may carry a power-of-two scale (ammc_split_rows_scaled_f32): `g_inv_scale` undoes it.
 #include "ammc_common.h"
 #include <hip/hip_fp16.h>
+#include <stdio.h>
 
 namespace ammc_s16 {
 
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
     int k = col0 + 4 * ls;
     k = k < a.kpad ? k : a.kpad - 4;
     int tap = k >> a.cin_log2;
-    tap = tap < d.ntaps - 1 ? tap : d.ntaps - 1;           // K padding: any valid address (those columns are never stored)
+    tap = tap < d.ntaps - 1 ? tap : d.ntaps - 1;           // K padding: any valid address (those columns are never stored: kvalid below)
     const int r = a.tap_w == 3 ? (tap * 11) >> 5 : (a.tap_w == 4 ? tap >> 2 : tap >> 1), s = tap - a.tap_w * r;
     a_toff[j] = (int64_t)r * d.a_rs + (int64_t)s * d.a_ps + (k & (d.cin - 1));
   }
@@ -199,6 +200,9 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
   const float inv = a.g_inv_scale ? a.g_inv_scale[0] : 1.f;
   constexpr float LO = 1.f / 2048.f;
   const bool a_hi = ((l31 >> 3) & 1) == 0;
+  // columns ntaps * cin .. kpad (cin 8 | 16 of a 3x3 window) were staged from the last tap's address: they stay as the caller
+  // zeroed them (they used to receive a copy of the last tap's columns; no reader ever used them)
+  const int kvalid = d.ntaps * d.cin;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
         const float other = __shfl_xor(t, 8);                         // the same against the other A plane
         if (a_hi) {
           const int row = row0 + wm * 32 + 16 * i + 8 * (r >> 3) + (r & 3) + 4 * h;
-          if (row < d.n && col < a.kpad)
+          if (row < d.n && col < kvalid)
             unsafeAtomicAdd(d.dw + (int64_t)row * a.kpad + col, (t + other * LO) * inv);
         }
       }
@@ -220,12 +224,13 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
 }
 
 // wgrad_tap_s16.hip: the halo-patch form; -12345 = not its case
-int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream);
+// `label` non-null: nothing is launched, the kernel's name goes to label[0..label_len) (ammc_conv_wgrad_s16_variant)
+int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, char* label, int label_len);
 
 }  // namespace ammc_s16
 using namespace ammc_s16;
 
-extern "C" int ammc_conv_wgrad_s16(const AmmcWgradDesc* desc, const float* g_inv_scale, void* stream) {
+static int wgrad_s16_dispatch(const AmmcWgradDesc* desc, const float* g_inv_scale, void* stream, char* label, int label_len) {
   if (!desc || !desc->g || !desc->a || !desc->dw || !desc->zeros) return AMMC_EINVAL;
   const AmmcWgradDesc& d = *desc;
   if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.n <= 0 || (d.n % 32)) return AMMC_EINVAL;
@@ -244,8 +249,12 @@ extern "C" int ammc_conv_wgrad_s16(const AmmcWgradDesc* desc, const float* g_inv
   a.tap_w = d.ntaps == 9 ? 3 : (d.ntaps == 16 ? 4 : 2);
   a.a_step = d.a_step > 1 ? d.a_step : 1;
   if (d.ntaps == 9 && a.a_step == 1) {                    // the halo-patch forms: stride-1 3x3 layers
-    const int rc = wgrad_tap_s16_try(d, g_inv_scale, a.kpad, (hipStream_t)stream);
+    const int rc = wgrad_tap_s16_try(d, g_inv_scale, a.kpad, (hipStream_t)stream, label, label_len);
     if (rc != -12345) return rc;
+  }
+  if (label) {
+    snprintf(label, label_len, "wgrad_s16");
+    return AMMC_OK;
   }
   constexpr size_t lds = (size_t)2 * 32 * (WS_BR + WS_BC) * sizeof(float);
   static bool attr_done = false;
@@ -267,4 +276,14 @@ extern "C" int ammc_conv_wgrad_s16(const AmmcWgradDesc* desc, const float* g_inv
   a.msplit = (a.nchunks + a.chunks_per_block - 1) / a.chunks_per_block;
   hipLaunchKernelGGL(wgrad_s16_kernel, dim3(tiles * a.msplit), dim3(WS_NT), lds, (hipStream_t)stream, a);
   return ammc_launch_status();
+}
+
+extern "C" int ammc_conv_wgrad_s16(const AmmcWgradDesc* desc, const float* g_inv_scale, void* stream) {
+  return wgrad_s16_dispatch(desc, g_inv_scale, stream, nullptr, 0);
+}
+
+extern "C" int ammc_conv_wgrad_s16_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len) {
+  if (!out || out_len < 48) return AMMC_EINVAL;
+  out[0] = 0;
+  return wgrad_s16_dispatch(desc, nullptr, nullptr, out, out_len);
 }

@@ -53,7 +53,9 @@
 // epilogue (AMMC_WGRAD_DBG ablations).
 #include "ammc_common.h"
 #include <hip/hip_fp16.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace ammc_s16 {
 
@@ -423,13 +425,21 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
 }
 
 template <int NG, int NA, int NP, int PH, int GW = 1, int ROLL = 0, int G11 = 0>
-static int launch_wgrad_tap3(WgradTap3Args a, hipStream_t stream) {
+static int launch_wgrad_tap3(WgradTap3Args a, hipStream_t stream, char* label, int label_len) {
   constexpr int W3_NT = 64 * NG * NA * NP;
   constexpr int TN = 32 * NG * GW, TC = 32 * NA;
   constexpr int AJ = ((PH + 2) * W3_HW * (TC / 4) + W3_NT - 1) / W3_NT;
   constexpr size_t lds = (size_t)(2 * PH * W3_PW * TN + (ROLL ? 4 * 2 * W3_HW * TC : 2 * AJ * W3_NT * 4)) * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = wgrad_tap3_s16_kernel<NG, NA, NP, PH, GW, ROLL, G11>;
+  if (label) {                       // launch nothing: the instance's name, template arguments as the dispatcher writes them
+    int n = snprintf(label, label_len, "wgrad_tap3_s16<%d, %d, %d, %d", NG, NA, NP, PH);
+    if ((GW != 1 || ROLL || G11) && n < label_len) n += snprintf(label + n, label_len - n, ", %d", GW);
+    if ((ROLL || G11) && n < label_len) n += snprintf(label + n, label_len - n, ", %d", ROLL);
+    if (G11 && n < label_len) n += snprintf(label + n, label_len - n, ", %d", G11);
+    if (n < label_len) snprintf(label + n, label_len - n, ">");
+    return AMMC_OK;
+  }
   if (!a.query) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds);
@@ -452,7 +462,9 @@ static int launch_wgrad_tap3(WgradTap3Args a, hipStream_t stream) {
 
 // Called by wgrad_tap_s16_try; -12345 = not this kernel's case.
 // `slabs` / `query`: see WgradTap3Args (query: the return value is the number of patch splits, or -12345)
-int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, float* slabs, int query) {
+// `label` non-null: nothing is launched, no HIP call is made, the instance's name goes to label (AMMC_OK, or -12345)
+int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, float* slabs, int query,
+                       char* label, int label_len) {
   if (d.height % 2 || d.width % W3_PW) return -12345;
   const int64_t gmax = (int64_t)3 * d.g_rs + (int64_t)(W3_PW - 1) * d.g_ps + d.n;
   const int64_t amax = (int64_t)5 * d.a_rs + (int64_t)(W3_PW + 1) * d.a_ps + d.cin;
@@ -480,16 +492,16 @@ int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpa
     // training path (tests/test_gpu_train.py: 1e-4 per tensor) see 2.1e-4 - the arithmetic would no longer be
     // fp32-equivalent, whatever the timed batch can resolve.
     static const int g11 = getenv("AMMC_WGRAD_G11") ? atoi(getenv("AMMC_WGRAD_G11")) : 0;
-    if (g11 && roll && d.n % 128 == 0) return launch_wgrad_tap3<4, 2, 1, 2, 1, 1, 1>(a, stream);
-    if (g11 && roll && d.n % 64 == 0) return launch_wgrad_tap3<2, 2, 2, 2, 1, 1, 1>(a, stream);
-    if (d.n % 128 == 0 && gw == 2) return launch_wgrad_tap3<2, 2, 1, 2, 2>(a, stream);
-    if (d.n % 128 == 0) return roll ? launch_wgrad_tap3<4, 2, 1, 2, 1, 1>(a, stream) : launch_wgrad_tap3<4, 2, 1, 2>(a, stream);
-    if (d.n % 64 == 0) return roll ? launch_wgrad_tap3<2, 2, 2, 2, 1, 1>(a, stream) : launch_wgrad_tap3<2, 2, 2, 2>(a, stream);
-    if (d.n == 32 && d.height % 4 == 0) return launch_wgrad_tap3<1, 2, 4, 4>(a, stream);    // the output layer
+    if (g11 && roll && d.n % 128 == 0) return launch_wgrad_tap3<4, 2, 1, 2, 1, 1, 1>(a, stream, label, label_len);
+    if (g11 && roll && d.n % 64 == 0) return launch_wgrad_tap3<2, 2, 2, 2, 1, 1, 1>(a, stream, label, label_len);
+    if (d.n % 128 == 0 && gw == 2) return launch_wgrad_tap3<2, 2, 1, 2, 2>(a, stream, label, label_len);
+    if (d.n % 128 == 0) return roll ? launch_wgrad_tap3<4, 2, 1, 2, 1, 1>(a, stream, label, label_len) : launch_wgrad_tap3<4, 2, 1, 2>(a, stream, label, label_len);
+    if (d.n % 64 == 0) return roll ? launch_wgrad_tap3<2, 2, 2, 2, 1, 1>(a, stream, label, label_len) : launch_wgrad_tap3<2, 2, 2, 2>(a, stream, label, label_len);
+    if (d.n == 32 && d.height % 4 == 0) return launch_wgrad_tap3<1, 2, 4, 4>(a, stream, label, label_len);    // the output layer
     return -12345;
   }
   // first layers: 8 / 16 / 32 input channels (one zero-padded 32-channel block)
-  if (d.cin <= 32 && d.n % 64 == 0 && d.height % 4 == 0) return launch_wgrad_tap3<2, 1, 4, 4>(a, stream);
+  if (d.cin <= 32 && d.n % 64 == 0 && d.height % 4 == 0) return launch_wgrad_tap3<2, 1, 4, 4>(a, stream, label, label_len);
   return -12345;
 }
 
@@ -538,26 +550,47 @@ extern "C" int64_t ammc_conv_wgrad_s16_slab_floats(const AmmcWgradDesc* desc) {
       (desc->cin & (desc->cin - 1)) || desc->batch <= 0 || desc->height <= 0 || desc->width <= 0)
     return 0;
   const int kpad = ((9 * desc->cin + 31) / 32) * 32;
-  const int ms = wgrad_tap3_s16_try(*desc, nullptr, kpad, nullptr, nullptr, 1);
+  const int ms = wgrad_tap3_s16_try(*desc, nullptr, kpad, nullptr, nullptr, 1, nullptr, 0);
   return ms <= 0 ? 0 : (int64_t)ms * desc->n * kpad;
 }
 
-extern "C" int ammc_conv_wgrad_s16_slabs(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs,
-                                         int64_t slab_floats, float* dw_oihw, int32_t cout, int32_t cin, void* stream) {
-  if (!desc || !desc->g || !desc->a || !desc->zeros || !slabs || !dw_oihw) return AMMC_EINVAL;
+// the slab entry; `label` non-null (ammc_conv_wgrad_s16_slabs_variant): nothing is launched, no HIP call, the workspace and
+// output arguments are not looked at, label = the instance's name + "+slabs<k>"
+static int wgrad_s16_slabs_dispatch(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs, int64_t slab_floats,
+                                    float* dw_oihw, int32_t cout, int32_t cin, void* stream, char* label, int label_len) {
+  if (!desc || !desc->g || !desc->a || !desc->zeros) return AMMC_EINVAL;
   const AmmcWgradDesc& d = *desc;
-  if (cout <= 0 || cout > d.n || cin <= 0 || cin > d.cin) return AMMC_EINVAL;
+  if (!label) {
+    if (!slabs || !dw_oihw) return AMMC_EINVAL;
+    if (cout <= 0 || cout > d.n || cin <= 0 || cin > d.cin) return AMMC_EINVAL;
+  }
   if (((uintptr_t)d.g | (uintptr_t)d.a | (uintptr_t)d.zeros) & 31) return AMMC_EINVAL;
   if ((d.g_bs | d.g_rs | d.g_ps | d.a_bs | d.a_rs | d.a_ps) & 7) return AMMC_EINVAL;
   const int64_t need = ammc_conv_wgrad_s16_slab_floats(desc);
   if (need <= 0) return AMMC_EUNSUP;
-  if (slab_floats < need) return AMMC_EINVAL;
+  if (!label && slab_floats < need) return AMMC_EINVAL;
   const int kpad = ((9 * d.cin + 31) / 32) * 32;
   const int msplit = (int)(need / ((int64_t)d.n * kpad));
-  const int rc = wgrad_tap3_s16_try(d, g_inv_scale, kpad, (hipStream_t)stream, slabs, 0);
+  const int rc = wgrad_tap3_s16_try(d, g_inv_scale, kpad, (hipStream_t)stream, slabs, 0, label, label_len);
   if (rc != AMMC_OK) return rc == -12345 ? AMMC_EUNSUP : rc;
+  if (label) {
+    const int len = (int)strlen(label);
+    snprintf(label + len, label_len - len, "+slabs%d", msplit);
+    return AMMC_OK;
+  }
   const int64_t total = (int64_t)cout * cin * 9;
   hipLaunchKernelGGL(reduce_unpack_wgrad_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64 * RU_G), 0, (hipStream_t)stream,
                      slabs, msplit, d.n, kpad, cout, cin, d.cin, dw_oihw);
   return ammc_launch_status();
+}
+
+extern "C" int ammc_conv_wgrad_s16_slabs(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs,
+                                         int64_t slab_floats, float* dw_oihw, int32_t cout, int32_t cin, void* stream) {
+  return wgrad_s16_slabs_dispatch(desc, g_inv_scale, slabs, slab_floats, dw_oihw, cout, cin, stream, nullptr, 0);
+}
+
+extern "C" int ammc_conv_wgrad_s16_slabs_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len) {
+  if (!out || out_len < 64) return AMMC_EINVAL;
+  out[0] = 0;
+  return wgrad_s16_slabs_dispatch(desc, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, out, out_len);
 }

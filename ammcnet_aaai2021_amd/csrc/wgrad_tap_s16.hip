@@ -17,6 +17,7 @@
 // Needs H % 4 == 0, W % 32 == 0, Cin % (16 NA) == 0, N % (16 NG) == 0; ammc_conv_wgrad_s16 falls back otherwise.
 #include "ammc_common.h"
 #include <hip/hip_fp16.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace ammc_s16 {
@@ -192,12 +193,16 @@ __global__ __launch_bounds__(WT_NT, 2) void wgrad_tap_s16_kernel(WgradTapArgs a)
 }
 
 template <int NG, int NA>
-static int launch_wgrad_tap(WgradTapArgs a, hipStream_t stream) {
+static int launch_wgrad_tap(WgradTapArgs a, hipStream_t stream, char* label, int label_len) {
   constexpr int TN = 16 * NG, TC = 16 * NA;
   constexpr int AJ = (WT_HPX * (TC / 4) + WT_NT - 1) / WT_NT;
   constexpr size_t lds = (size_t)(2 * WT_PX * TN + 2 * AJ * WT_NT * 4) * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = wgrad_tap_s16_kernel<NG, NA>;
+  if (label) {                       // launch nothing: the instance's name
+    snprintf(label, label_len, "wgrad_tap_s16<%d, %d>", NG, NA);
+    return AMMC_OK;
+  }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds);
   if (e != hipSuccess) return (int)e;
@@ -215,14 +220,19 @@ static int launch_wgrad_tap(WgradTapArgs a, hipStream_t stream) {
 }
 
 // wgrad_tap3_s16.hip: three MFMAs per product block, 128 x 64 channel tiles (N % 128 == 0, Cin % 64 == 0)
-int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, float* slabs, int query);
+int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, float* slabs, int query,
+                       char* label, int label_len);
 
 // Called by ammc_conv_wgrad_s16 after its argument checks; -12345 = not this kernel's case.
-int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream) {
+// `label` non-null: nothing is launched, the instance's name goes to label (ammc_conv_wgrad_s16_variant).
+// In the default mode every descriptor this file's kernels accept is taken by wgrad_tap3_s16_try first (cin is a power of
+// two: cin <= 32 with n % 64 == 0, H % 4 == 0, or cin % 64 == 0 with n % 64 == 0), so they run under AMMC_WGRAD_TAP=2 only
+// (tests/test_wgrad_cases_host.py enumerates the grid).
+int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, char* label, int label_len) {
   static const int mode = getenv("AMMC_WGRAD_TAP") ? atoi(getenv("AMMC_WGRAD_TAP")) : 1;
   if (!mode) return -12345;
   if (mode != 2) {                                         // AMMC_WGRAD_TAP=2: this file's kernels only (A/Bs)
-    const int rc = wgrad_tap3_s16_try(d, g_inv_scale, kpad, stream, nullptr, 0);
+    const int rc = wgrad_tap3_s16_try(d, g_inv_scale, kpad, stream, nullptr, 0, label, label_len);
     if (rc != -12345) return rc;
   }
   if (d.height % WT_PH || d.width % WT_PW) return -12345;
@@ -239,7 +249,7 @@ int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad
   a.tiles_x = d.width / WT_PW;
   a.tiles_y = d.height / WT_PH;
   a.npatch = d.batch * a.tiles_x * a.tiles_y;
-  return wide ? launch_wgrad_tap<8, 1>(a, stream) : launch_wgrad_tap<4, 2>(a, stream);
+  return wide ? launch_wgrad_tap<8, 1>(a, stream, label, label_len) : launch_wgrad_tap<4, 2>(a, stream, label, label_len);
 }
 
 }  // namespace ammc_s16

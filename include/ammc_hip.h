@@ -364,6 +364,16 @@ int ammc_conv_wgrad_s16(const AmmcWgradDesc* desc, const float* g_inv_scale, voi
 int64_t ammc_conv_wgrad_s16_slab_floats(const AmmcWgradDesc* desc);
 int ammc_conv_wgrad_s16_slabs(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs, int64_t slab_floats,
                               float* dw_oihw, int32_t cout, int32_t cin, void* stream);
+/* Which kernel ammc_conv_wgrad_s16 launches for this descriptor, as the NUL-terminated name of the instance
+ * ("wgrad_tap3_s16<2, 2, 2, 2, 1, 1>", "wgrad_tap_s16<8, 1>", "wgrad_s16": template arguments as the dispatcher writes
+ * them, trailing defaults left out), without launching anything and without a HIP call: the same argument checks (all
+ * four pointers of the descriptor included) and the same dispatch code, environment switches included, with the launch
+ * replaced by the label; the same status codes as ammc_conv_wgrad_s16 for the same descriptor.  out_len >= 48.
+ * ammc_conv_wgrad_s16_slabs_variant: the same for ammc_conv_wgrad_s16_slabs (desc->dw is not looked at): the instance's
+ * name + "+slabs<k>", k = the slabs the launch writes = ammc_conv_wgrad_s16_slab_floats / (n * kpad); AMMC_EUNSUP where
+ * the slab entry has no kernel for the descriptor (slab_floats == 0), AMMC_EINVAL as that entry.  out_len >= 64. */
+int ammc_conv_wgrad_s16_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len);
+int ammc_conv_wgrad_s16_slabs_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len);
 /* packed gradient -> the module's parameter layout */
 int ammc_unpack_conv_wgrad_f32(const float* packed, int32_t cout, int32_t cin, int32_t ksize, int32_t cin_p,
                                float* out_oihw, void* stream);

@@ -16,9 +16,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-# W % 32 == 0, H even, n % 64 == 0, cin % 64 == 0 go to the three-MFMA halo-patch kernel (csrc/wgrad_tap3_s16.hip);
-# W % 32 == 0 and H % 4 == 0 with (n % 128, cin % 16) or (n % 64, cin % 32) to the four-product one
-# (csrc/wgrad_tap_s16.hip), the rest to the im2col one (csrc/wgrad_s16.hip); AMMC_WGRAD_TAP=2 / =0 force the latter two
+# W % 32 == 0, H even, cin % 64 == 0 with n % 64 == 0 (or n == 32, H % 4 == 0), and cin <= 32 with n % 64 == 0, H % 4 == 0 go to
+# the three-MFMA halo-patch kernel (csrc/wgrad_tap3_s16.hip), the rest to the im2col one (csrc/wgrad_s16.hip).  NO shape here
+# reaches the four-product kernel (csrc/wgrad_tap_s16.hip): the three-MFMA dispatcher takes everything it would accept, it
+# runs under AMMC_WGRAD_TAP=2 only (=0: im2col for every 3x3).  Both switch forms and the label of every case:
+# tests/test_gpu_wgrad_kernels.py, tests/test_wgrad_cases_host.py
 @pytest.mark.parametrize("B,H,W,cin,n,gmag", [(2, 32, 32, 64, 128, 1.0), (3, 20, 24, 128, 64, 3e-7), (2, 16, 16, 16, 64, 1e-6),
                                                (1, 9, 7, 32, 32, 1.0), (4, 64, 64, 64, 64, 2e-8), (1, 8, 64, 16, 128, 1e-5),
                                                (2, 16, 32, 128, 64, 1.0), (3, 12, 96, 256, 256, 1e-3),

@@ -1,0 +1,590 @@
+"""Cases of the S16 weight-gradient kernels - csrc/wgrad_tap3_s16.hip (nine instances + the slab reduce),
+wgrad_tap_s16.hip (two instances), wgrad_s16.hip (the im2col form: 3x3, 4x4 stride 1 | 2, the 2x2 stride-2 window of a
+ConvTranspose) - behind `ammc_conv_wgrad_s16` / `ammc_conv_wgrad_s16_slabs`, shared by tests/test_wgrad_cases_host.py
+(labels, routing, references, sensitivity, refusals: no device) and tests/test_gpu_wgrad_kernels.py (the kernels against
+fp64).  A helper module like tests/patch_cases.py, not a test.
+
+A case is one launch as the training engine builds it: the shape, the padded and the true channel counts, where the
+operands live (dense, the upper half of a buffer twice as wide, a window of a larger buffer, the ConvTranspose's odd
+crop), which operand carries the power-of-two scale, the label `ammc_conv_wgrad_s16_variant` must answer, whether the slab
+entry takes it, and the environment switch (read once per process by the dispatchers) under which it runs.
+
+Kinds (H, W: the pixel space of g)
+  conv3  dW[o][c][r][s] = sum G[b][y][x][o] A[b][y + r - 1][x + s - 1][c]         Conv2d(k 3, padding 1)
+  conv4  dW[o][c][r][s] = sum G[b][y][x][o] A[b][st y + r - 2][st x + s - 2][c]   Conv2d(k 4, padding 2, stride st = a_step);
+         a is (H - 1) x (W - 1) at stride 1, (2H - 2 + a_odd) x (2W - 2 + a_odd) at stride 2
+  convt  dW[i][o][dy][dx] = sum X[b][y][x][i] dY[b][2y + dy][2x + dx][o]          ConvTranspose2d(k 2, stride 2): "g" = the
+         layer input X (n = its channels), "a" = the output gradient dY at twice the resolution (cin = its channels)
+
+Guarded buffers: every operand lives inside a flat buffer filled with the bit pattern SENT (a NaN as a float and as a pair
+of halfs): the pads before and behind, the other half of a sliced buffer, everything of a larger buffer outside the
+window, g's halo ring (no kernel reads it), the odd row / column of the ConvTranspose crop.  a's own zero ring (one pixel,
+two for 4x4) is the convolution's padding and stays zero.  `zeros` is exactly 128 zero floats followed by SENT.  A read of
+any of these turns the result into NaN."""
+import ctypes as C
+import os
+from dataclasses import dataclass, replace
+
+import torch
+import torch.nn.functional as F
+
+from ammcnet_aaai2021_amd import _lib, synthetic as S
+from ammcnet_aaai2021_amd._lib import AmmcWgradDesc
+
+GATE = 3e-6                # of max|want|: the project's gate for this entry (tests/test_gpu_wgrad_s16.py)
+GATE_G11 = (3e-6, 3e-4)    # AMMC_WGRAD_G11=1: at least / at most (the same file)
+GATE_SLAB = 2e-6           # slab form against the atomics form, of max|dw| (the same file)
+SENS_MIN = 10              # an operand reduced to its hi half must move the fp64 truth by at least this many gates
+DEV = "cuda:0"
+SENT = 0x7FC07FC0
+PAD = 1024                 # floats (4 KB) of sentinel before and behind every guarded buffer
+SWITCHES = ("AMMC_WGRAD_TAP", "AMMC_WGRAD_GW", "AMMC_WGRAD_ROLL", "AMMC_WGRAD_G11")
+
+_T3 = "wgrad_tap3_s16<%s>"
+R64, R128 = _T3 % "2, 2, 2, 2, 1, 1", _T3 % "4, 2, 1, 2, 1, 1"          # the rolling-halo instances (default)
+O32, F32C = _T3 % "1, 2, 4, 4", _T3 % "2, 1, 4, 4"                      # output layer; first layers (cin <= 32)
+P64, P128 = _T3 % "2, 2, 2, 2", _T3 % "4, 2, 1, 2"                      # AMMC_WGRAD_ROLL=0
+GW2 = _T3 % "2, 2, 1, 2, 2"                                             # AMMC_WGRAD_GW=2
+G64, G128 = _T3 % "2, 2, 2, 2, 1, 1, 1", _T3 % "4, 2, 1, 2, 1, 1, 1"    # AMMC_WGRAD_G11=1
+TAP8, TAP4 = "wgrad_tap_s16<8, 1>", "wgrad_tap_s16<4, 2>"               # AMMC_WGRAD_TAP=2
+IM2COL = "wgrad_s16"
+TAP3_INSTANCES = [R64, R128, O32, F32C, P64, P128, GW2, G64, G128]
+TAP_INSTANCES = [TAP8, TAP4]
+INSTANCES = TAP3_INSTANCES + TAP_INSTANCES + [IM2COL]
+
+
+@dataclass(frozen=True)
+class Case:
+    name: str
+    kind: str                # conv3 | conv4 | convt
+    B: int
+    H: int                   # pixel space of g
+    W: int
+    n: int                   # rows of the packed gradient (g's padded channels)
+    cin: int                 # a's padded channels (a power of two >= 8)
+    label: str               # what ammc_conv_wgrad_s16_variant must answer
+    cout: int = 0            # true rows (0: n)
+    cin_true: int = 0        # true input channels (0: cin)
+    a_step: int = 1
+    a_odd: int = 0           # conv4 stride 2: one more row / column of a (an odd input size)
+    gmag: float = 1.0        # magnitude of the operand that carries the scale (the gradient)
+    geom: str = "dense"      # dense | slice (upper half of a 2x-wide buffer) | crop (window of a larger buffer) | oddcrop (convt)
+    scaled: str = "g"        # which operand went through ammc_split_rows_scaled_f32: g | a | "" (g_inv_scale = NULL)
+    slab: bool = False       # the slab entry takes it
+    switch: str = ""         # "" or "AMMC_WGRAD_TAP=2", ...: the process environment it runs under
+    hot: tuple = ()          # placement case: ((b, y, x), ...) - g is `gmag` at spot j in channel j and zero elsewhere
+
+    @property
+    def inv_null(self):
+        return self.scaled == ""
+
+    @property
+    def ntaps(self):
+        return {"conv3": 9, "conv4": 16, "convt": 4}[self.kind]
+
+    @property
+    def rows(self):
+        return self.cout or self.n
+
+    @property
+    def chans(self):
+        return self.cin_true or self.cin
+
+    @property
+    def kpad(self):
+        return (self.ntaps * self.cin + 31) // 32 * 32
+
+
+def _c(name, kind, B, H, W, n, cin, label, **kw):
+    return Case(name, kind, B, H, W, n, cin, label, **kw)
+
+
+# hot spots of the placement cases (B 2, 8 x 64): the four image corners, both sides of the patch-row seams of the two-row
+# (1 | 2) and four-row (3 | 4) patches, both sides of the x = 31 | 32 patch seam, the last row of image 0 and the first of
+# image 1, the last pixel of the last image
+HOT = ((0, 0, 0), (0, 0, 63), (0, 7, 0), (0, 7, 63), (0, 1, 10), (0, 2, 10), (0, 3, 40), (0, 4, 40), (0, 5, 31), (0, 5, 32),
+       (0, 7, 20), (1, 0, 20), (1, 7, 63))
+TINY = 2.0 ** -20
+
+
+def _default_cases():
+    c3 = lambda name, B, H, W, n, cin, label, **kw: _c(name, "conv3", B, H, W, n, cin, label, **kw)
+    sl = dict(slab=True)
+    out = [
+        # ---- wgrad_tap3_s16<2, 2, 2, 2, 1, 1>: 64 x 64 channel tiles, two-row patches, rolling halo ---------------------------
+        c3("r64-one-patch", 1, 2, 32, 64, 64, R64, **sl),
+        c3("r64-run-crosses-columns-and-images", 2, 4, 64, 64, 64, R64, gmag=3e-7, geom="slice", **sl),      # 8 patches, one run
+        c3("r64-split-starts-mid-column", 1, 10, 96, 64, 64, R64, gmag=1e-3, geom="crop", **sl),             # 15 patches, runs of 8 + 7
+        c3("r64-one-patch-columns", 3, 2, 96, 64, 64, R64, scaled="", **sl),
+        c3("r64-n192", 1, 4, 32, 192, 64, R64, gmag=2e-8, **sl),                                             # three row tiles
+        # ---- <4, 2, 1, 2, 1, 1>: 128 x 64 ---------------------------------------------------------------------------------------
+        c3("r128-one-patch", 1, 2, 32, 128, 64, R128, scaled="", **sl),
+        c3("r128-n256-cin128", 2, 6, 32, 256, 128, R128, gmag=1e-5, geom="slice", **sl),                     # 2 x 2 tiles
+        c3("r128-crop", 2, 10, 64, 128, 64, R128, gmag=1e-2, geom="crop", **sl),                         # 20 patches, runs of 7 + 7 + 6
+        # ---- <1, 2, 4, 4>: the output layer, 3 true filters of 32 -----------------------------------------------------------------
+        c3("o32-cout3", 1, 4, 32, 32, 64, O32, cout=3, gmag=1e-4, **sl),
+        c3("o32-cout3-b2-8x64", 2, 8, 64, 32, 64, O32, cout=3, scaled="", geom="crop", **sl),
+        c3("o32-cout3-slice", 2, 4, 32, 32, 64, O32, cout=3, gmag=1e-6, geom="slice", **sl),
+        # ---- <2, 1, 4, 4>: the first layers, cin <= 32 (one zero-padded 32-channel block) -----------------------------------------
+        c3("first-cin8of3-n64", 1, 4, 32, 64, 8, F32C, cin_true=3, gmag=1e-6, **sl),
+        c3("first-cin16of12-n128-b3", 3, 12, 32, 128, 16, F32C, cin_true=12, scaled="", geom="slice", **sl),
+        c3("first-cin32-n64-b3", 3, 12, 32, 64, 32, F32C, gmag=3e-4, geom="crop", **sl),
+        c3("first-cin8of3-n128-b3", 3, 12, 32, 128, 8, F32C, cin_true=3, gmag=1e-1, **sl),
+        # ---- the im2col form, 3x3: what both halo-patch dispatchers decline ---------------------------------------------------------
+        c3("im2col-m63", 1, 9, 7, 32, 32, IM2COL),                                                            # one short chunk
+        c3("im2col-n96", 1, 4, 32, 96, 64, IM2COL, gmag=1e-5, geom="slice"),                                  # n % 64
+        c3("im2col-n32-h6", 1, 6, 32, 32, 64, IM2COL, cout=3, scaled="", geom="crop"),                        # H % 4
+        c3("im2col-n160-cin16", 2, 5, 9, 160, 16, IM2COL, cin_true=12, gmag=1e-3),                            # row-tile tail, kpad 160
+        c3("im2col-cin8-kpad96", 2, 7, 5, 64, 8, IM2COL, cin_true=3, gmag=2e-8),                              # kpad < one column tile
+        c3("im2col-msplit3-short-last", 2, 15, 21, 64, 32, IM2COL, gmag=1e-2),                                # M 630: 20 chunks as 7 + 7 + 6
+        # ---- ntaps 16: PixelDiscriminator ---------------------------------------------------------------------------------------------
+        _c("c4-s2-cin8of3-n64", "conv4", 2, 9, 7, 64, 8, IM2COL, cin_true=3, a_step=2, gmag=1e-6),
+        _c("c4-s1-cin64-n32of1", "conv4", 1, 8, 6, 32, 64, IM2COL, cout=1, a_step=1, gmag=3e-4),              # the head
+        _c("c4-s2-odd-cin64-n64", "conv4", 1, 6, 5, 64, 64, IM2COL, a_step=2, a_odd=1, scaled=""),
+        _c("c4-s1-cin8of3-n32of1", "conv4", 2, 5, 9, 32, 8, IM2COL, cout=1, cin_true=3, a_step=1, gmag=1.0, geom="slice"),
+        # ---- ntaps 4: ConvTranspose; the scale sits on the a side (the output gradient), as the engine passes it -----------------------
+        _c("convt-exact-n128-co64", "convt", 2, 5, 7, 128, 64, IM2COL, a_step=2, scaled="a", gmag=1e-5),
+        _c("convt-odd-crop", "convt", 2, 6, 6, 64, 32, IM2COL, a_step=2, scaled="a", gmag=1e-3, geom="oddcrop"),
+        _c("convt-unscaled", "convt", 1, 3, 5, 64, 32, IM2COL, a_step=2, scaled=""),
+    ]
+    # ---- placement: one-hot gradients (value 1, and 2^-20 through the rescaling) on every default 3x3 kernel ------------------------
+    for tag, n, cin, lab, slab in (("r64", 64, 64, R64, True), ("r128", 128, 64, R128, True), ("o32", 32, 64, O32, True),
+                                   ("first", 64, 32, F32C, True), ("im2col", 96, 64, IM2COL, False)):
+        out.append(c3(f"place-{tag}-one", 2, 8, 64, n, cin, lab, hot=HOT, gmag=1.0, slab=slab))
+        out.append(c3(f"place-{tag}-tiny", 2, 8, 64, n, cin, lab, hot=HOT, gmag=TINY, slab=slab))
+    return out
+
+
+def _switch_cases(default):
+    by = {c.name: c for c in default}
+    out = []
+
+    def add(switch, tag, base, label, **kw):
+        out.append(replace(by[base], name=f"{tag}-{base}", switch=switch, label=label, **kw))
+    # AMMC_WGRAD_TAP=2: the four-product halo-patch kernels only (no slab form: the three-MFMA kernel's)
+    c3 = lambda name, B, H, W, n, cin, label, **kw: _c(name, "conv3", B, H, W, n, cin, label, switch="AMMC_WGRAD_TAP=2", **kw)
+    out += [
+        c3("tap8-n128-cin16", 1, 4, 32, 128, 16, TAP8, cin_true=12, gmag=1e-4, slab=True),
+        c3("tap8-n128-cin16-b2", 2, 8, 64, 128, 16, TAP8, scaled="", geom="slice", slab=True),
+        c3("tap8-n128-cin64", 1, 4, 32, 128, 64, TAP8, gmag=2e-8, geom="crop", slab=True),
+        c3("tap8-n128-cin64-b2", 2, 8, 64, 128, 64, TAP8, gmag=1e-2, slab=True),
+        c3("tap4-n64-cin32", 1, 4, 32, 64, 32, TAP4, scaled="", slab=True),
+        c3("tap4-n64-cin32-b2", 2, 8, 64, 64, 32, TAP4, gmag=1e-6, geom="crop", slab=True),
+        c3("tap4-n64-cin128", 1, 4, 32, 64, 128, TAP4, gmag=1e-3, geom="slice", slab=True),
+        c3("tap4-n64-cin128-b2", 2, 8, 64, 64, 128, TAP4, gmag=3e-7, slab=True),
+        c3("place-tap8-one", 2, 8, 64, 128, 16, TAP8, hot=HOT, slab=True),
+        c3("place-tap8-tiny", 2, 8, 64, 128, 16, TAP8, hot=HOT, gmag=TINY, slab=True),
+        c3("place-tap4-one", 2, 8, 64, 64, 32, TAP4, hot=HOT, slab=True),
+        c3("place-tap4-tiny", 2, 8, 64, 64, 32, TAP4, hot=HOT, gmag=TINY, slab=True),
+    ]
+    # AMMC_WGRAD_TAP=0: the im2col form for every 3x3 (the slab entry has its own dispatch and still takes the descriptor)
+    for c in default:                   # every case of the four halo-patch kernels, parity and placement
+        if c.kind == "conv3" and c.label != IM2COL:
+            add("AMMC_WGRAD_TAP=0", "tap0", c.name, IM2COL)
+    for base in ("r128-one-patch", "r128-n256-cin128", "r128-crop", "place-r128-one", "place-r128-tiny"):
+        add("AMMC_WGRAD_GW=2", "gw2", base, GW2)
+    for base, lab in (("r64-one-patch", P64), ("r64-run-crosses-columns-and-images", P64), ("r64-split-starts-mid-column", P64),
+                      ("r64-one-patch-columns", P64), ("r64-n192", P64), ("place-r64-one", P64), ("place-r64-tiny", P64),
+                      ("r128-one-patch", P128), ("r128-n256-cin128", P128), ("r128-crop", P128), ("place-r128-one", P128),
+                      ("place-r128-tiny", P128)):
+        add("AMMC_WGRAD_ROLL=0", "roll0", base, lab)
+    for base, lab in (("r64-one-patch", G64), ("r64-run-crosses-columns-and-images", G64), ("r64-split-starts-mid-column", G64),
+                      ("r64-one-patch-columns", G64), ("r64-n192", G64), ("place-r64-one", G64), ("place-r64-tiny", G64),
+                      ("r128-one-patch", G128), ("r128-n256-cin128", G128), ("r128-crop", G128), ("place-r128-one", G128),
+                      ("place-r128-tiny", G128)):
+        add("AMMC_WGRAD_G11=1", "g11", base, lab)
+    return out
+
+
+DEFAULT = _default_cases()
+CASES = DEFAULT + _switch_cases(DEFAULT)
+BY_NAME = {c.name: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+PARITY = [c for c in CASES if not c.hot]
+PLACEMENT = [c for c in CASES if c.hot]
+
+
+def current_switch() -> str:
+    """the switch this process runs under, as a case names it ("" = none of them set)"""
+    here = [f"{k}={os.environ[k]}" for k in SWITCHES if k in os.environ]
+    return here[0] if len(here) == 1 else ("" if not here else "+".join(here))
+
+
+def active(cases):
+    """the cases of `cases` this process can run: those of its own switch setting"""
+    sw = current_switch()
+    return [c for c in cases if c.switch == sw]
+
+
+def gate(c: Case):
+    """(at least, at most) of max|want|"""
+    return GATE_G11 if c.switch == "AMMC_WGRAD_G11=1" else (0.0, GATE)
+
+
+# ---- operands and references --------------------------------------------------------------------------------------------------
+class Ops:
+    pass
+
+
+def s16_round(t: torch.Tensor) -> torch.Tensor:
+    """what an fp32 tensor decodes to after the S16 split (ammc_common.h ammc_s16_split8): hi = half(v), lo = half((v - hi) 2^11)"""
+    t = t.float()
+    hi = t.half().float()
+    lo = ((t - hi) * 2048.0).half().float()
+    return hi.double() + lo.double() / 2048.0
+
+
+def hi_only(t: torch.Tensor) -> torch.Tensor:
+    return t.float().half().double()
+
+
+def a_size(c: Case):
+    if c.kind == "conv3":
+        return c.H, c.W
+    if c.kind == "conv4":
+        return (c.H - 1, c.W - 1) if c.a_step == 1 else (2 * c.H - 2 + c.a_odd, 2 * c.W - 2 + c.a_odd)
+    return 2 * c.H, 2 * c.W
+
+
+def a_halo(c: Case) -> int:
+    return 2 if c.kind == "conv4" else 1
+
+
+def wshape(c: Case):
+    k = {"conv3": 3, "conv4": 4, "convt": 2}[c.kind]
+    return (c.rows, c.chans, k, k)
+
+
+def host_ops(c: Case) -> Ops:
+    """g [B][rows][H][W] and a [B][chans][ah][aw] (NCHW fp32, true channel counts).  The gradient-like operand (the one
+    that carries the scale; g when neither does) is uniform in +-gmag, the activation-like one a ReLU-clamped uniform with
+    a wide range (a quarter of the values zero, the rest up to 2).  Placement cases: a on a 2^-16 grid (exact in S16), g
+    one-hot."""
+    o = Ops()
+    t = "wc-" + (c.name.split("-", 1)[1] if c.switch else c.name)          # a switch case shares its default case's operands
+    ah, aw = a_size(c)
+    if c.hot:
+        a = torch.round(S.hashed_uniform(t + "a", (c.B, c.chans, ah, aw)) * 65536.0) / 65536.0
+        g = torch.zeros(c.B, c.rows, c.H, c.W)
+        for j, (b, y, x) in enumerate(c.hot):
+            g[b, j, y, x] = c.gmag
+        o.g, o.a = g, a
+        return o
+    g = S.hashed_uniform(t + "g", (c.B, c.rows, c.H, c.W))
+    a = S.hashed_uniform(t + "a", (c.B, c.chans, ah, aw))
+    act = lambda v: (v * 2.0 + 0.5).clamp_min(0.0).clamp_max(2.0) if c.kind != "convt" else v * 1.5
+    if c.scaled == "a":
+        o.g, o.a = act(g), a * c.gmag
+    else:
+        o.g, o.a = g * c.gmag, act(a)
+    return o
+
+
+def reference(c: Case, dtype=torch.float64, g=None, a=None, o=None) -> torch.Tensor:
+    """the weight gradient of the reference operator by autograd in `dtype`: dL/dw of L = sum(op(a, w) * g) for conv2d,
+    L = sum(conv_transpose2d(g, w) * a) for the ConvTranspose form"""
+    if g is None or a is None:
+        o = o or host_ops(c)
+        g = o.g if g is None else g
+        a = o.a if a is None else a
+    g, a = g.to(dtype), a.to(dtype)
+    w = torch.zeros(wshape(c), dtype=dtype, requires_grad=True)
+    if c.kind == "conv3":
+        y, up = F.conv2d(a, w, padding=1), g
+    elif c.kind == "conv4":
+        y, up = F.conv2d(a, w, padding=2, stride=c.a_step), g
+        y = y[:, :, :c.H, :c.W]
+    else:
+        y, up = F.conv_transpose2d(g, w, stride=2), a
+    assert y.shape == up.shape, (c.name, y.shape, up.shape)
+    (y * up).sum().backward()
+    return w.grad.detach()
+
+
+def reference_unfolded(c: Case, g: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """the same sum written out tap by tap (no autograd, no convolution): the independent formulation of the host test"""
+    g, a = g.double(), a.double()
+    k = wshape(c)[2]
+    out = torch.zeros(wshape(c), dtype=torch.float64)
+    if c.kind == "convt":
+        for dy in range(2):
+            for dx in range(2):
+                out[:, :, dy, dx] = torch.einsum("bihw,bohw->io", g, a[:, :, dy::2, dx::2])
+        return out
+    h, st = a_halo(c), c.a_step
+    ap = F.pad(a, (h, h + 2, h, h + 2))                                      # (room for the windows of a stride-2 tail)
+    for r in range(k):
+        for s in range(k):
+            win = ap[:, :, r:r + st * (c.H - 1) + 1:st, s:s + st * (c.W - 1) + 1:st]
+            out[:, :, r, s] = torch.einsum("bohw,bchw->oc", g, win)
+    return out
+
+
+def rel_err(got, want) -> float:
+    got, want = got.double().cpu(), want.double().cpu()
+    return float((got - want).abs().max() / want.abs().max())
+
+
+def pow2_scale(t: torch.Tensor) -> float:
+    """the power of two ammc_split_rows_scaled_f32 multiplies by: max|t| lands in [2^10, 2^11)"""
+    m, e = torch.frexp(t.abs().max().double())               # max = m 2^e, m in [0.5, 1)
+    return 2.0 ** (11 - int(e))
+
+
+def _as_split(c: Case, o: Ops, role: str, f):
+    """operand `role` through f (s16_round | hi_only) as the device splits it: the scaled one at its power-of-two scale"""
+    t = o.g if role == "g" else o.a
+    if c.scaled != role:
+        return f(t)
+    k = pow2_scale(t)
+    return f(t.double() * k) / k
+
+
+def sensitivity(c: Case, o: Ops):
+    """how far the fp64 truth moves, in gates, when g / when a is reduced to its hi half"""
+    g, a = _as_split(c, o, "g", s16_round), _as_split(c, o, "a", s16_round)
+    want = reference(c, g=g, a=a)
+    sg = rel_err(reference(c, g=_as_split(c, o, "g", hi_only), a=a), want) / GATE
+    sa = rel_err(reference(c, g=g, a=_as_split(c, o, "a", hi_only)), want) / GATE
+    return sg, sa
+
+
+def placement_want(c: Case, o: Ops) -> torch.Tensor:
+    """row j = the 3 x 3 neighbourhood of hot spot j in a (zero beyond the image), times the hot value; every other row 0"""
+    ap = F.pad(o.a, (1, 1, 1, 1))
+    want = torch.zeros(wshape(c))
+    for j, (b, y, x) in enumerate(c.hot):
+        want[j] = ap[b, :, y:y + 3, x:x + 3] * c.gmag
+    return want
+
+
+# ---- descriptors ------------------------------------------------------------------------------------------------------------------
+def _layout(c: Case, role: str):
+    """(container shape [B][hb][wb][ctot], (y, x, channel) offset of the operand's halo corner in it, channels, halo)"""
+    if role == "g":
+        H, W, ch, halo = c.H, c.W, c.n, 1
+    else:
+        (H, W), ch, halo = a_size(c), c.cin, a_halo(c)
+    hb, wb = H + 2 * halo, W + 2 * halo
+    if c.geom == "slice":
+        return (c.B, hb, wb, 2 * ch), (0, 0, ch), ch, halo
+    if c.geom == "crop":
+        return (c.B, hb + 3, wb + 5, ch), (1, 1, 0), ch, halo
+    if c.geom == "oddcrop" and role == "a":
+        return (c.B, hb + 1, wb + 1, 2 * ch), (0, 0, ch), ch, halo
+    return (c.B, hb, wb, ch), (0, 0, 0), ch, halo
+
+
+def desc(c: Case, g=0x10000000, a=0x20000000, dw=0x30000000, zeros=0x40000000) -> AmmcWgradDesc:
+    """the descriptor of the case over containers at the given base addresses (fake ones for the label)"""
+    d = AmmcWgradDesc()
+    for role, base in (("g", g), ("a", a)):
+        shape, (oy, ox, oc), ch, halo = _layout(c, role)
+        ps = shape[3]
+        rs = shape[2] * ps
+        bs = shape[1] * rs
+        corner = oy * rs + ox * ps + oc
+        pix0 = corner + halo * (rs + ps)
+        if role == "g":
+            d.g, d.g_bs, d.g_rs, d.g_ps = base + 4 * pix0, bs, rs, ps
+        else:                        # conv3 / conv4: the corner of the zero ring; convt: pixel (0, 0)
+            d.a, d.a_bs, d.a_rs, d.a_ps = base + 4 * (pix0 if c.kind == "convt" else corner), bs, rs, ps
+    d.dw, d.zeros = dw, zeros
+    d.batch, d.height, d.width, d.n, d.cin, d.ntaps, d.a_step = c.B, c.H, c.W, c.n, c.cin, c.ntaps, c.a_step
+    return d
+
+
+def variant(d: AmmcWgradDesc):
+    """(status, label) of ammc_conv_wgrad_s16_variant: the library's own dispatch, nothing launched, no device"""
+    buf = C.create_string_buffer(96)
+    rc = _lib.load().ammc_conv_wgrad_s16_variant(C.byref(d), buf, 96)
+    return rc, buf.value.decode()
+
+
+def slabs_variant(d: AmmcWgradDesc):
+    buf = C.create_string_buffer(96)
+    rc = _lib.load().ammc_conv_wgrad_s16_slabs_variant(C.byref(d), buf, 96)
+    return rc, buf.value.decode()
+
+
+def slab_count(d: AmmcWgradDesc) -> int:
+    kpad = (9 * d.cin + 31) // 32 * 32
+    return int(_lib.load().ammc_conv_wgrad_s16_slab_floats(C.byref(d))) // (d.n * kpad)
+
+
+def refusals():
+    """[(what, status the entry returns, expected status)] of ammc_conv_wgrad_s16 (through its label query, which runs the
+    same checks; the launch entry itself where a refusal comes before anything is launched) and of the slab entry"""
+    lib = _lib.load()
+    base = BY_NAME["r64-one-patch"]
+
+    def q(c=base, **kw):
+        d = desc(c)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def lab(d):
+        return variant(d)[0]
+
+    def launch(d):
+        return lib.ammc_conv_wgrad_s16(C.byref(d), None, None)
+
+    def slabs(d, floats=None, cout=64, cin=64, ws=0x50000000, out=0x60000000):
+        need = int(lib.ammc_conv_wgrad_s16_slab_floats(C.byref(d)))
+        return lib.ammc_conv_wgrad_s16_slabs(C.byref(d), None, ws, need if floats is None else floats, out, cout, cin, None)
+    d0 = desc(base)
+    need = int(lib.ammc_conv_wgrad_s16_slab_floats(C.byref(d0)))
+    assert need == 2 * 64 * 576, need                           # one patch split x two row groups
+    out = []
+    for what, d, want in (
+            ("n % 32", q(n=48), -1), ("cin = 48", q(cin=48), -2), ("cin = 4", q(cin=4), -2), ("ntaps 1", q(ntaps=1), -2),
+            ("a_step 3", q(a_step=3), -2), ("g off 32-byte alignment", q(g=d0.g + 16), -1), ("a off alignment", q(a=d0.a + 16), -1),
+            ("zeros off alignment", q(zeros=d0.zeros + 4), -1), ("g_rs % 8", q(g_rs=d0.g_rs + 4), -1), ("a_ps % 8", q(a_ps=d0.a_ps + 4), -1),
+            ("a_bs % 8", q(a_bs=d0.a_bs + 2), -1), ("null g", q(g=None), -1), ("null a", q(a=None), -1), ("null dw", q(dw=None), -1),
+            ("null zeros", q(zeros=None), -1), ("batch 0", q(batch=0), -1)):
+        got = lab(d)
+        out.append((what + " (query)", got, want))
+        if got != 0:                 # (fake addresses: the launch entry is only asked about what the same checks refuse)
+            out.append((what + " (launch entry)", launch(d), want))
+    out.append(("null descriptor (query)", lib.ammc_conv_wgrad_s16_variant(None, C.create_string_buffer(96), 96), -1))
+    out.append(("short label buffer", lib.ammc_conv_wgrad_s16_variant(C.byref(d0), C.create_string_buffer(16), 16), -1))
+    out += [
+        ("slabs: n % 32", slabs(q(n=48), cout=32), -2), ("slabs: cin = 48", slabs(q(cin=48), cin=32), -2), ("slabs: ntaps 16", slabs(q(ntaps=16)), -2),
+        ("slabs: a_step 2", slabs(q(a_step=2)), -2), ("slabs: W % 32", slabs(q(width=24)), -2), ("slabs: n 96", slabs(q(n=96)), -2),
+        ("slabs: g off alignment", slabs(q(g=d0.g + 16)), -1), ("slabs: stride % 8", slabs(q(a_rs=d0.a_rs + 4)), -1),
+        ("slabs: null g", slabs(q(g=None)), -1), ("slabs: null zeros", slabs(q(zeros=None)), -1),
+        ("slabs: null workspace", slabs(d0, ws=None), -1), ("slabs: null dw_oihw", slabs(d0, out=None), -1),
+        ("slabs: cout > n", slabs(d0, cout=65), -1), ("slabs: cout 0", slabs(d0, cout=0), -1),
+        ("slabs: cin > desc->cin", slabs(d0, cin=65), -1), ("slabs: cin 0", slabs(d0, cin=0), -1),
+        ("slabs: workspace one float short", slabs(d0, floats=need - 1), -1),
+        ("slabs query: n 96", slabs_variant(q(n=96))[0], -2), ("slabs query: null a", slabs_variant(q(a=None))[0], -1),
+        ("slabs query: dw is not looked at", slabs_variant(q(dw=None))[0], 0),
+    ]
+    return out
+
+
+# ---- the device half ------------------------------------------------------------------------------------------------------------
+def _ptr(t: torch.Tensor, off: int = 0) -> int:
+    return t.data_ptr() + 4 * off
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+class Guarded:
+    """`count` elements in the middle of a flat int32 buffer: PAD sentinels, the body (filled with `fill`, an int32 bit
+    pattern), PAD sentinels"""
+
+    def __init__(self, count, fill=SENT):
+        self.flat = torch.full((PAD + count + PAD,), SENT, dtype=torch.int32, device=DEV)
+        self.bits = self.flat[PAD:PAD + count]
+        self.bits.fill_(fill)
+        self.t = self.bits.view(torch.float32)
+
+    def pads_intact(self) -> bool:
+        return bool((self.flat[:PAD] == SENT).all()) and bool((self.flat[-PAD:] == SENT).all())
+
+
+def _nhwc(t, cp, halo):
+    """NCHW (host) -> dense device NHWC with `halo` zero pixels and channels zero-padded to cp"""
+    B, Cc, H, W = t.shape
+    buf = torch.zeros(B, H + 2 * halo, W + 2 * halo, cp, device=DEV)
+    buf[:, halo:halo + H, halo:halo + W, :Cc] = t.to(DEV).permute(0, 2, 3, 1)
+    return buf
+
+
+def _decode(buf16):
+    """S16 twin [..., C] (fp32 storage: groups of [8 hi | 8 lo] halfs) -> float64 [..., C]"""
+    ch = buf16.shape[-1]
+    h = buf16.contiguous().view(torch.float16).reshape(*buf16.shape[:-1], ch // 8, 2, 8).double()
+    return (h[..., 0, :] + h[..., 1, :] / 2048.0).reshape(*buf16.shape[:-1], ch)
+
+
+def _operand(c: Case, role: str, t_nchw, scaled: bool, keep: list):
+    """-> (Guarded container, float offset of the container's first element, the operand as the kernel sees it [NCHW true
+    channels, float64, device], inv tensor or None)"""
+    lib, s = _lib.load(), _stream()
+    shape, (oy, ox, oc), ch, halo = _layout(c, role)
+    d32 = _nhwc(t_nchw, ch, halo)
+    d16 = torch.empty_like(d32)
+    inv = None
+    if scaled:
+        amax = torch.zeros(256, dtype=torch.int32, device=DEV)
+        inv = torch.empty(8, device=DEV)
+        _lib.check(lib.ammc_absmax_bits_f32(_ptr(d32), d32.numel(), amax.data_ptr(), s), "absmax")
+        _lib.check(lib.ammc_split_rows_scaled_f32(_ptr(d32), d32.numel(), _ptr(d16), amax.data_ptr(), _ptr(inv), 8, s), "split scaled")
+        keep.append(amax)
+    else:
+        _lib.check(lib.ammc_split_rows_f32(_ptr(d32), d32.numel(), _ptr(d16), s), "split")
+    seen = _decode(d16)
+    if inv is not None:
+        seen = seen * inv[0].double()
+    B, hb, wb = d32.shape[:3]
+    seen = seen[:, halo:hb - halo, halo:wb - halo, :t_nchw.shape[1]].permute(0, 3, 1, 2).contiguous()
+    cont = Guarded(shape[0] * shape[1] * shape[2] * shape[3])
+    view = cont.bits.view(shape)
+    region = view[:, oy:oy + hb, ox:ox + wb, oc:oc + ch]
+    region.copy_(d16.view(torch.int32))
+    if role == "g" or c.kind == "convt":           # no kernel reads these halo rings; a's ring (conv3 / conv4) is the zero padding
+        region[:, 0], region[:, -1], region[:, :, 0], region[:, :, -1] = SENT, SENT, SENT, SENT
+    return cont, seen, inv
+
+
+def run_case(c: Case, o: Ops) -> dict:
+    """builds the S16 twins with the library's split kernels inside sentinel-filled containers, launches the atomics form
+    twice into a guarded zeroed buffer and, where the case has one, the slab form twice into NaN-filled guarded buffers.
+    Returns label, status, packed (after one launch), dw (unpacked, true shape), dw_twice, g_seen / a_seen (decoded
+    operands, scale undone), guards (dict of booleans), and for the slab form slab_status, dws, slab_same, slab_label"""
+    lib, s = _lib.load(), _stream()
+    keep = []
+    gc, g_seen, g_inv = _operand(c, "g", o.g, c.scaled == "g", keep)
+    ac, a_seen, a_inv = _operand(c, "a", o.a, c.scaled == "a", keep)
+    inv = g_inv if g_inv is not None else a_inv
+    zeros = Guarded(128, fill=0)
+    dwg = Guarded(c.n * c.kpad, fill=0)
+    d = desc(c, g=_ptr(gc.t), a=_ptr(ac.t), dw=_ptr(dwg.t), zeros=_ptr(zeros.t))
+    r = dict(g_seen=g_seen, a_seen=a_seen, inv=(float(inv[0]) if inv is not None else None))
+    r["status_q"], r["label"] = variant(d)
+    inv_p = _ptr(inv) if inv is not None else None
+
+    def unpack(packed):
+        out = torch.full(wshape(c), float("nan"), device=DEV)
+        if c.kind == "convt":
+            assert c.rows == c.n and c.chans == c.cin
+            _lib.check(lib.ammc_unpack_convt_wgrad_f32(_ptr(packed), c.n, c.cin, _ptr(out), s), "unpack_convt")
+        else:
+            _lib.check(lib.ammc_unpack_conv_wgrad_f32(_ptr(packed), c.rows, c.chans, wshape(c)[2], c.cin, _ptr(out), s), "unpack")
+        return out
+    rc = lib.ammc_conv_wgrad_s16(C.byref(d), inv_p, s)
+    r["status"] = rc
+    if rc != 0:
+        return r
+    torch.cuda.synchronize()
+    r["packed"] = dwg.t.clone().view(c.n, c.kpad)
+    r["dw"] = unpack(dwg.t)
+    _lib.check(lib.ammc_conv_wgrad_s16(C.byref(d), inv_p, s), "second launch")
+    torch.cuda.synchronize()
+    r["dw_twice"] = unpack(dwg.t)
+    intact = lambda: all(x.pads_intact() for x in (gc, ac, zeros, dwg))
+    r["guards"] = dict(atomics=intact())
+    need = int(lib.ammc_conv_wgrad_s16_slab_floats(C.byref(d))) if c.kind == "conv3" else 0
+    r["need"] = need
+    r["slab_status_q"], r["slab_label"] = slabs_variant(d)
+    if need > 0:
+        outs = []
+        for _ in range(2):
+            slabs = Guarded(need, fill=SENT)                 # NaN: every element that is read must have been written
+            og = Guarded(c.rows * c.chans * 9, fill=SENT)    # dw_oihw of the TRUE shape
+            rc = lib.ammc_conv_wgrad_s16_slabs(C.byref(d), inv_p, _ptr(slabs.t), need, _ptr(og.t), c.rows, c.chans, s)
+            r["slab_status"] = rc
+            if rc != 0:
+                return r
+            torch.cuda.synchronize()
+            r["guards"]["slab"] = r["guards"].get("slab", True) and slabs.pads_intact() and og.pads_intact() and intact()
+            outs.append(og.t.clone().view(wshape(c)))
+        r["dws"] = outs[0]
+        r["slab_same"] = torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
+    del keep
+    return r
