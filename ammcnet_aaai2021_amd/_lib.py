@@ -116,6 +116,12 @@ SIGNATURES = {
     "ammc_conv_wgrad_s16_slabs_variant": (C.c_int, [C.POINTER(AmmcWgradDesc), C.c_char_p, _i32]),
     "ammc_conv_wgrad_s16_slab_floats": (C.c_int64, [C.POINTER(AmmcWgradDesc)]),
     "ammc_conv_wgrad_s16_slabs": (C.c_int, [C.POINTER(AmmcWgradDesc), _p, _p, _i64, _p, _i32, _i32, _p]),
+    "ammc_conv_wgrad_s16_det_floats": (C.c_int64, [C.POINTER(AmmcWgradDesc)]),
+    "ammc_conv_wgrad_s16_det": (C.c_int, [C.POINTER(AmmcWgradDesc), _p, _p, _i64, _p]),
+    "ammc_conv_wgrad_s16_det_variant": (C.c_int, [C.POINTER(AmmcWgradDesc), C.c_char_p, _i32]),
+    "ammc_conv_wgrad_f32_det_floats": (C.c_int64, [C.POINTER(AmmcWgradDesc)]),
+    "ammc_conv_wgrad_f32_det": (C.c_int, [C.POINTER(AmmcWgradDesc), _p, _i64, _p]),
+    "ammc_conv_wgrad_f32_det_variant": (C.c_int, [C.POINTER(AmmcWgradDesc), C.c_char_p, _i32]),
     "ammc_unpack_conv_wgrad_f32": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "ammc_unpack_convt_wgrad_f32": (C.c_int, [_p, _i32, _i32, _p, _p]),
     "ammc_pack_conv_dgrad_weight_f32": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),

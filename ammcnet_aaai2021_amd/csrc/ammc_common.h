@@ -65,6 +65,10 @@ int ammc_opt_memory_rt();
 // (1: opt-in, measured 1 % faster at 262144 rows); -1 / 0 = fused (default); AMMC_MEMORY_SPLIT / ammc_set_option
 int ammc_opt_memory_split();
 
+// wgrad_tap3_s16.hip: the fixed-order sum of the deterministic weight-gradient forms (ammc_conv_wgrad_{s16,f32}_det):
+// out[e] = slabs[e] + slabs[total + e] + ... + slabs[(msplit - 1) * total + e], added in that order, e < total
+int ammc_reduce_wgrad_slabs(const float* slabs, int msplit, int64_t total, float* out, hipStream_t stream);
+
 static inline int ammc_ilog2(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;

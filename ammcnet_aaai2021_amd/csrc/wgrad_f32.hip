@@ -20,12 +20,17 @@
 // combined with fp32 global atomics (rows of 128 B per wave instruction: the full-rate shape).
 // Out-of-range pixels of the last chunk read G from a caller-supplied row of zeros.
 // Roofline: MFMA fp32, same arithmetic intensity as the forward kernel.
+// Deterministic form (ammc_conv_wgrad_f32_det, WgradArgs::slabs): every workgroup STORES its tile into the slab of its
+// pixel split ([msplit][n][kpad], plain stores) and ammc_reduce_wgrad_slabs writes dw[r][c] = slab 0 + slab 1 + ... in
+// that order; one split stores straight into dw.  Same splits, same tiles, same accumulators as the atomics form.
 #include "ammc_common.h"
+#include <stdio.h>
 
 namespace ammc_impl {
 
 struct WgradArgs {
   AmmcWgradDesc d;
+  float* slabs;                  // non-null: the deterministic form - [msplit][n][kpad], stored, not added (dw itself when msplit == 1)
   int M, kpad, cin_log2;
   int row_tiles, col_tiles, msplit, chunks_per_block, nchunks;
 };
@@ -156,7 +161,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(WgradArgs a) {
   }
 #undef WG_ISSUE
 
-  // ---- combine: fp32 atomics into the packed gradient -------------------------------
+  // ---- combine: fp32 atomics into the packed gradient, or (deterministic form) stores into this split's slab ----
+  float* const slab = a.slabs ? a.slabs + (int64_t)ms * d.n * a.kpad : nullptr;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = col0 + (wn * TN + j) * 32 + l31;
@@ -166,16 +172,40 @@ __global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(WgradArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = row0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row < d.n) unsafeAtomicAdd(d.dw + (int64_t)row * a.kpad + col, acc[i][j][r]);
+        if (row < d.n) {
+          if (slab) slab[(int64_t)row * a.kpad + col] = acc[i][j][r];
+          else unsafeAtomicAdd(d.dw + (int64_t)row * a.kpad + col, acc[i][j][r]);
+        }
       }
     }
   }
 }
 
+// the dW tile and the pixel splits for this descriptor: a function of the descriptor alone (the 4 x 256 workgroups are a
+// constant of the dispatcher, not a device query).  Rows per tile by n (128 | 64 | 32), 128 columns in every instance.
+static int wgrad_f32_tile_rows(int n) { return n % 128 == 0 ? 128 : (n % 64 == 0 ? 64 : 32); }
+
+static void wgrad_f32_plan(WgradArgs& a) {
+  const int BR = wgrad_f32_tile_rows(a.d.n), BC = 128;
+  a.row_tiles = (a.d.n + BR - 1) / BR;
+  a.col_tiles = (a.kpad + BC - 1) / BC;
+  a.nchunks = (a.M + 31) / 32;
+  const int tiles = a.row_tiles * a.col_tiles;
+  // enough workgroups for ~4 per CU, at least 8 chunks (256 pixels) each
+  int msplit = (4 * 256 + tiles - 1) / tiles;
+  const int max_split = (a.nchunks + 7) / 8;
+  if (msplit > max_split) msplit = max_split;
+  if (msplit < 1) msplit = 1;
+  a.chunks_per_block = (a.nchunks + msplit - 1) / msplit;
+  a.msplit = (a.nchunks + a.chunks_per_block - 1) / a.chunks_per_block;       // (every split owns at least one chunk)
+}
+
+// `a` is planned (wgrad_f32_plan) and a.slabs is set
 template <int WGM, int WGN, int TM, int TN>
-int launch_wgrad(WgradArgs a, hipStream_t stream, int num_cu_hint) {
+int launch_wgrad(const WgradArgs& a, hipStream_t stream) {
   constexpr int BR = WGM * TM * 32;
   constexpr int BC = WGN * TN * 32;
+  static_assert(BC == 128, "wgrad_f32_plan");
   constexpr size_t lds = (size_t)2 * 32 * (BR + BC) * sizeof(float);
   auto kern = wgrad_f32_kernel<WGM, WGN, TM, TN>;
   if (lds > 48 * 1024) {
@@ -183,18 +213,7 @@ int launch_wgrad(WgradArgs a, hipStream_t stream, int num_cu_hint) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  a.row_tiles = (a.d.n + BR - 1) / BR;
-  a.col_tiles = (a.kpad + BC - 1) / BC;
-  a.nchunks = (a.M + 31) / 32;
-  const int tiles = a.row_tiles * a.col_tiles;
-  // enough workgroups for ~4 per CU, at least 8 chunks (256 pixels) each
-  int msplit = (4 * num_cu_hint + tiles - 1) / tiles;
-  const int max_split = (a.nchunks + 7) / 8;
-  if (msplit > max_split) msplit = max_split;
-  if (msplit < 1) msplit = 1;
-  a.chunks_per_block = (a.nchunks + msplit - 1) / msplit;
-  a.msplit = (a.nchunks + a.chunks_per_block - 1) / a.chunks_per_block;
-  hipLaunchKernelGGL(kern, dim3(tiles * a.msplit), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(a.row_tiles * a.col_tiles * a.msplit), dim3(256), lds, stream, a);
   return ammc_launch_status();
 }
 
@@ -226,26 +245,70 @@ __global__ __launch_bounds__(256) void unpack_convt_wgrad_kernel(const float* __
 }  // namespace ammc_impl
 using namespace ammc_impl;
 
-extern "C" int ammc_conv_wgrad_f32(const AmmcWgradDesc* desc, void* stream) {
-  if (!desc || !desc->g || !desc->a || !desc->dw || !desc->zeros) return AMMC_EINVAL;
+// the argument checks of both entries and the plan; `pointers`: also the operand addresses and strides (a launch, a label)
+static int wgrad_f32_prepare(const AmmcWgradDesc* desc, bool pointers, WgradArgs& a) {
+  if (!desc || (pointers && (!desc->g || !desc->a || !desc->dw || !desc->zeros))) return AMMC_EINVAL;
   const AmmcWgradDesc& d = *desc;
   if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.n <= 0 || (d.n % 32)) return AMMC_EINVAL;
   if (d.ntaps != 9 && d.ntaps != 4 && d.ntaps != 1 && d.ntaps != 16) return AMMC_EINVAL;
   if (d.ntaps != 1 && (d.cin < 4 || (d.cin & (d.cin - 1)))) return AMMC_EUNSUP;
   if (d.ntaps == 1 && (d.cin <= 0 || d.cin % 32)) return AMMC_EUNSUP;
-  if (((uintptr_t)d.g | (uintptr_t)d.a | (uintptr_t)d.zeros) & 15) return AMMC_EINVAL;
-  if ((d.g_bs | d.g_rs | d.g_ps | d.a_bs | d.a_rs | d.a_ps) & 3) return AMMC_EINVAL;
+  if (pointers) {
+    if (((uintptr_t)d.g | (uintptr_t)d.a | (uintptr_t)d.zeros) & 15) return AMMC_EINVAL;
+    if ((d.g_bs | d.g_rs | d.g_ps | d.a_bs | d.a_rs | d.a_ps) & 3) return AMMC_EINVAL;
+  }
   const int64_t M = (int64_t)d.batch * d.height * d.width;
   if (M >= (1LL << 31)) return AMMC_EUNSUP;
-  WgradArgs a;
   a.d = d;
+  a.slabs = nullptr;
   a.M = (int)M;
   a.kpad = ((d.ntaps * d.cin + 31) / 32) * 32;
   a.cin_log2 = ammc_ilog2(d.cin);
-  hipStream_t s = (hipStream_t)stream;
-  if (d.n % 128 == 0) return launch_wgrad<2, 2, 2, 2>(a, s, 256);   // 128 rows x 128 cols
-  if (d.n % 64 == 0) return launch_wgrad<1, 4, 2, 1>(a, s, 256);    // 64 rows x 128 cols
-  return launch_wgrad<1, 4, 1, 1>(a, s, 256);                       // 32 rows x 128 cols (outc, first layers)
+  wgrad_f32_plan(a);
+  return AMMC_OK;
+}
+
+static int wgrad_f32_launch(const WgradArgs& a, hipStream_t s) {
+  switch (wgrad_f32_tile_rows(a.d.n)) {
+    case 128: return launch_wgrad<2, 2, 2, 2>(a, s);      // 128 rows x 128 cols
+    case 64: return launch_wgrad<1, 4, 2, 1>(a, s);       // 64 rows x 128 cols
+    default: return launch_wgrad<1, 4, 1, 1>(a, s);       // 32 rows x 128 cols (outc, first layers)
+  }
+}
+
+extern "C" int ammc_conv_wgrad_f32(const AmmcWgradDesc* desc, void* stream) {
+  WgradArgs a;
+  const int rc = wgrad_f32_prepare(desc, true, a);
+  return rc != AMMC_OK ? rc : wgrad_f32_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int64_t ammc_conv_wgrad_f32_det_floats(const AmmcWgradDesc* desc) {
+  WgradArgs a;
+  if (wgrad_f32_prepare(desc, false, a) != AMMC_OK || a.msplit <= 1) return 0;   // refused, or one split: stored straight into dw
+  return (int64_t)a.msplit * a.d.n * a.kpad;
+}
+
+extern "C" int ammc_conv_wgrad_f32_det(const AmmcWgradDesc* desc, float* slabs, int64_t slab_floats, void* stream) {
+  WgradArgs a;
+  int rc = wgrad_f32_prepare(desc, true, a);
+  if (rc != AMMC_OK) return rc;
+  const int64_t total = (int64_t)a.d.n * a.kpad;
+  if (a.msplit > 1 && (!slabs || slab_floats < a.msplit * total)) return AMMC_EINVAL;
+  a.slabs = a.msplit > 1 ? slabs : a.d.dw;
+  rc = wgrad_f32_launch(a, (hipStream_t)stream);
+  if (rc != AMMC_OK || a.msplit == 1) return rc;
+  return ammc_reduce_wgrad_slabs(slabs, a.msplit, total, a.d.dw, (hipStream_t)stream);
+}
+
+extern "C" int ammc_conv_wgrad_f32_det_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len) {
+  if (!out || out_len < 48) return AMMC_EINVAL;
+  out[0] = 0;
+  WgradArgs a;
+  const int rc = wgrad_f32_prepare(desc, true, a);
+  if (rc != AMMC_OK) return rc;
+  const int br = wgrad_f32_tile_rows(a.d.n);
+  snprintf(out, out_len, "wgrad_f32<%s>+det%d", br == 128 ? "2, 2, 2, 2" : (br == 64 ? "1, 4, 2, 1" : "1, 4, 1, 1"), a.msplit);
+  return AMMC_OK;
 }
 
 extern "C" int ammc_unpack_conv_wgrad_f32(const float* packed, int32_t cout, int32_t cin, int32_t ksize,

@@ -17,10 +17,14 @@
 // wave) conflict free; the DMA applies the same permutation on its source side.
 // A workgroup (8 waves as 4 x 2, each 32 rows x 64 columns) owns 128 rows (n) x 128 columns (k) of dWp and a slice of
 // the pixels; fp32 atomics combine the slices.  The kernel is bound by its LDS-DMA traffic (16 MAC per staged byte).
+// Deterministic form (ammc_conv_wgrad_s16_det, WgradS16Args::slabs): every workgroup STORES its tile into the slab of its
+// pixel split ([msplit][n][kpad], plain stores, the K padding as zeros) and ammc_reduce_wgrad_slabs (wgrad_tap3_s16.hip)
+// writes dw[r][c] = slab 0 + slab 1 + ... in that order; one split stores straight into dw.  Same splits, same tiles.
 // G may carry a power-of-two scale (ammc_split_rows_scaled_f32): `g_inv_scale` undoes it.
 #include "ammc_common.h"
 #include <hip/hip_fp16.h>
 #include <stdio.h>
+#include <atomic>
 
 namespace ammc_s16 {
 
@@ -31,6 +35,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 struct WgradS16Args {
   AmmcWgradDesc d;
   const float* g_inv_scale;
+  float* slabs;                  // non-null: the deterministic form - [msplit][n][kpad], stored, not added (dw itself when msplit == 1)
   int M, kpad, cin_log2;
   int row_tiles, col_tiles, msplit, chunks_per_block, nchunks;
   int tap_w, a_step;             // window width (3, 4 or 2) and the stride of the window origin in `a` (1 or 2)
@@ -203,6 +208,9 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
   // columns ntaps * cin .. kpad (cin 8 | 16 of a 3x3 window) were staged from the last tap's address: they stay as the caller
   // zeroed them (they used to receive a copy of the last tap's columns; no reader ever used them)
   const int kvalid = d.ntaps * d.cin;
+  // the deterministic form: the slab of this pixel split; every element [n][kpad] of it is written (the K padding as zeros:
+  // the reduce reads whole slabs and nobody zeroed them)
+  float* const slab = a.slabs ? a.slabs + (int64_t)ms * d.n * a.kpad : nullptr;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -215,8 +223,11 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
         const float other = __shfl_xor(t, 8);                         // the same against the other A plane
         if (a_hi) {
           const int row = row0 + wm * 32 + 16 * i + 8 * (r >> 3) + (r & 3) + 4 * h;
-          if (row < d.n && col < kvalid)
+          if (slab) {
+            if (row < d.n && col < a.kpad) slab[(int64_t)row * a.kpad + col] = col < kvalid ? (t + other * LO) * inv : 0.f;
+          } else if (row < d.n && col < kvalid) {
             unsafeAtomicAdd(d.dw + (int64_t)row * a.kpad + col, (t + other * LO) * inv);
+          }
         }
       }
     }
@@ -230,41 +241,9 @@ int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad
 }  // namespace ammc_s16
 using namespace ammc_s16;
 
-static int wgrad_s16_dispatch(const AmmcWgradDesc* desc, const float* g_inv_scale, void* stream, char* label, int label_len) {
-  if (!desc || !desc->g || !desc->a || !desc->dw || !desc->zeros) return AMMC_EINVAL;
-  const AmmcWgradDesc& d = *desc;
-  if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.n <= 0 || (d.n % 32)) return AMMC_EINVAL;
-  if ((d.ntaps != 9 && d.ntaps != 16 && d.ntaps != 4) || d.a_step < 0 || d.a_step > 2) return AMMC_EUNSUP;
-  if (d.cin < 8 || (d.cin & (d.cin - 1))) return AMMC_EUNSUP;
-  if (((uintptr_t)d.g | (uintptr_t)d.a | (uintptr_t)d.zeros) & 31) return AMMC_EINVAL;
-  if ((d.g_bs | d.g_rs | d.g_ps | d.a_bs | d.a_rs | d.a_ps) & 7) return AMMC_EINVAL;
-  const int64_t M = (int64_t)d.batch * d.height * d.width;
-  if (M >= (1LL << 31)) return AMMC_EUNSUP;
-  WgradS16Args a;
-  a.d = d;
-  a.g_inv_scale = g_inv_scale;
-  a.M = (int)M;
-  a.kpad = ((d.ntaps * d.cin + 31) / 32) * 32;
-  a.cin_log2 = ammc_ilog2(d.cin);
-  a.tap_w = d.ntaps == 9 ? 3 : (d.ntaps == 16 ? 4 : 2);
-  a.a_step = d.a_step > 1 ? d.a_step : 1;
-  if (d.ntaps == 9 && a.a_step == 1) {                    // the halo-patch forms: stride-1 3x3 layers
-    const int rc = wgrad_tap_s16_try(d, g_inv_scale, a.kpad, (hipStream_t)stream, label, label_len);
-    if (rc != -12345) return rc;
-  }
-  if (label) {
-    snprintf(label, label_len, "wgrad_s16");
-    return AMMC_OK;
-  }
-  constexpr size_t lds = (size_t)2 * 32 * (WS_BR + WS_BC) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_s16_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
-  a.row_tiles = (d.n + WS_BR - 1) / WS_BR;
+// the pixel splits of wgrad_s16_kernel for this descriptor: a function of the descriptor alone (no device query, no switch)
+static void wgrad_s16_plan(WgradS16Args& a) {
+  a.row_tiles = (a.d.n + WS_BR - 1) / WS_BR;
   a.col_tiles = (a.kpad + WS_BC - 1) / WS_BC;
   a.nchunks = (a.M + 31) / 32;
   const int tiles = a.row_tiles * a.col_tiles;
@@ -273,9 +252,65 @@ static int wgrad_s16_dispatch(const AmmcWgradDesc* desc, const float* g_inv_scal
   if (msplit > max_split) msplit = max_split;
   if (msplit < 1) msplit = 1;
   a.chunks_per_block = (a.nchunks + msplit - 1) / msplit;
-  a.msplit = (a.nchunks + a.chunks_per_block - 1) / a.chunks_per_block;
-  hipLaunchKernelGGL(wgrad_s16_kernel, dim3(tiles * a.msplit), dim3(WS_NT), lds, (hipStream_t)stream, a);
+  a.msplit = (a.nchunks + a.chunks_per_block - 1) / a.chunks_per_block;       // (every split owns at least one chunk)
+}
+
+// the argument checks of both entries and the plan; `pointers`: also the operand addresses and strides (a launch, a label)
+static int wgrad_s16_prepare(const AmmcWgradDesc* desc, const float* g_inv_scale, bool pointers, WgradS16Args& a) {
+  if (!desc || (pointers && (!desc->g || !desc->a || !desc->dw || !desc->zeros))) return AMMC_EINVAL;
+  const AmmcWgradDesc& d = *desc;
+  if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.n <= 0 || (d.n % 32)) return AMMC_EINVAL;
+  if ((d.ntaps != 9 && d.ntaps != 16 && d.ntaps != 4) || d.a_step < 0 || d.a_step > 2) return AMMC_EUNSUP;
+  if (d.cin < 8 || (d.cin & (d.cin - 1))) return AMMC_EUNSUP;
+  if (pointers) {
+    if (((uintptr_t)d.g | (uintptr_t)d.a | (uintptr_t)d.zeros) & 31) return AMMC_EINVAL;
+    if ((d.g_bs | d.g_rs | d.g_ps | d.a_bs | d.a_rs | d.a_ps) & 7) return AMMC_EINVAL;
+  }
+  const int64_t M = (int64_t)d.batch * d.height * d.width;
+  if (M >= (1LL << 31)) return AMMC_EUNSUP;
+  a.d = d;
+  a.g_inv_scale = g_inv_scale;
+  a.slabs = nullptr;
+  a.M = (int)M;
+  a.kpad = ((d.ntaps * d.cin + 31) / 32) * 32;
+  a.cin_log2 = ammc_ilog2(d.cin);
+  a.tap_w = d.ntaps == 9 ? 3 : (d.ntaps == 16 ? 4 : 2);
+  a.a_step = d.a_step > 1 ? d.a_step : 1;
+  wgrad_s16_plan(a);
+  return AMMC_OK;
+}
+
+// `a` is prepared and a.slabs is set
+static int wgrad_s16_launch(const WgradS16Args& a, hipStream_t stream) {
+  constexpr size_t lds = (size_t)2 * 32 * (WS_BR + WS_BC) * sizeof(float);
+  // the LDS attribute once per DEVICE (one flag for the process would miss the second device)
+  constexpr int MAX_DEV = 64;
+  static std::atomic<bool> attr_done[MAX_DEV];
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV || !attr_done[dev].load(std::memory_order_relaxed)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_s16_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    if (dev >= 0 && dev < MAX_DEV) attr_done[dev].store(true, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL(wgrad_s16_kernel, dim3(a.row_tiles * a.col_tiles * a.msplit), dim3(WS_NT), lds, stream, a);
   return ammc_launch_status();
+}
+
+// ammc_conv_wgrad_s16 and its label query (`label` non-null: nothing is launched, no HIP call)
+static int wgrad_s16_dispatch(const AmmcWgradDesc* desc, const float* g_inv_scale, void* stream, char* label, int label_len) {
+  WgradS16Args a;
+  const int rc = wgrad_s16_prepare(desc, g_inv_scale, true, a);
+  if (rc != AMMC_OK) return rc;
+  if (a.d.ntaps == 9 && a.a_step == 1) {                    // the halo-patch forms: stride-1 3x3 layers
+    const int rt = wgrad_tap_s16_try(a.d, g_inv_scale, a.kpad, (hipStream_t)stream, label, label_len);
+    if (rt != -12345) return rt;
+  }
+  if (label) {
+    snprintf(label, label_len, "wgrad_s16");
+    return AMMC_OK;
+  }
+  return wgrad_s16_launch(a, (hipStream_t)stream);
 }
 
 extern "C" int ammc_conv_wgrad_s16(const AmmcWgradDesc* desc, const float* g_inv_scale, void* stream) {
@@ -286,4 +321,35 @@ extern "C" int ammc_conv_wgrad_s16_variant(const AmmcWgradDesc* desc, char* out,
   if (!out || out_len < 48) return AMMC_EINVAL;
   out[0] = 0;
   return wgrad_s16_dispatch(desc, nullptr, nullptr, out, out_len);
+}
+
+// The deterministic form: wgrad_s16_kernel for EVERY descriptor the checks accept (the halo-patch dispatchers and their
+// switches are not asked), slabs + the fixed-order reduce.
+extern "C" int64_t ammc_conv_wgrad_s16_det_floats(const AmmcWgradDesc* desc) {
+  WgradS16Args a;
+  if (wgrad_s16_prepare(desc, nullptr, false, a) != AMMC_OK || a.msplit <= 1) return 0;   // refused, or one split: stored straight into dw
+  return (int64_t)a.msplit * a.d.n * a.kpad;
+}
+
+extern "C" int ammc_conv_wgrad_s16_det(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs, int64_t slab_floats,
+                                       void* stream) {
+  WgradS16Args a;
+  int rc = wgrad_s16_prepare(desc, g_inv_scale, true, a);
+  if (rc != AMMC_OK) return rc;
+  const int64_t total = (int64_t)a.d.n * a.kpad;
+  if (a.msplit > 1 && (!slabs || slab_floats < a.msplit * total)) return AMMC_EINVAL;
+  a.slabs = a.msplit > 1 ? slabs : a.d.dw;
+  rc = wgrad_s16_launch(a, (hipStream_t)stream);
+  if (rc != AMMC_OK || a.msplit == 1) return rc;
+  return ammc_reduce_wgrad_slabs(slabs, a.msplit, total, a.d.dw, (hipStream_t)stream);
+}
+
+extern "C" int ammc_conv_wgrad_s16_det_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len) {
+  if (!out || out_len < 48) return AMMC_EINVAL;
+  out[0] = 0;
+  WgradS16Args a;
+  const int rc = wgrad_s16_prepare(desc, nullptr, true, a);
+  if (rc != AMMC_OK) return rc;
+  snprintf(out, out_len, "wgrad_s16+det%d", a.msplit);
+  return AMMC_OK;
 }

@@ -506,44 +506,70 @@ int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpa
 }
 
 // slabs [msplit][n][kpad] (k = tap * cin_p + c) -> OIHW [cout][cin][3][3]: 64 consecutive elements of the packed row x
-// RU_G slab groups per workgroup; thread (e, g) sums the slabs m = g, g + RU_G, ... of element e with eight loads in
+// G slab groups per workgroup; thread (e, g) sums the slabs m = g, g + G, ... of element e with eight loads in
 // flight, the groups are added through LDS in a fixed order (deterministic, unlike the atomics it replaces).
 // (One thread per element walking all slabs - the first form - left the 64 -> 64 layers with 144 workgroups of serial
 // 512-deep chains: 75 MB in 31 us.)
+// PACKED (the deterministic forms of the implicit-GEMM kernels, ammc_reduce_wgrad_slabs): the output is the packed
+// gradient itself, out[e] = slab 0 [e] + slab 1 [e] + ... + slab msplit-1 [e], added IN THAT ORDER: one group, the eight
+// loads in flight go into one accumulator one after the other (at most 512 slabs of a few thousand elements: the chain is
+// short, the loads are what takes the time).  `n` = 1 and `kpad` = the elements of a slab then; cout / cin / cin_p unused.
 constexpr int RU_G = 4;
-__global__ __launch_bounds__(64 * RU_G) void reduce_unpack_wgrad_kernel(const float* __restrict__ slabs, int msplit, int n, int kpad,
-                                                                       int cout, int cin, int cin_p, float* __restrict__ out) {
-  __shared__ float part[RU_G][64];
-  const int64_t total = (int64_t)cout * cin * 9;
+template <int G, bool PACKED>
+__global__ __launch_bounds__(64 * G) void reduce_unpack_wgrad_kernel(const float* __restrict__ slabs, int msplit, int64_t n, int64_t kpad,
+                                                                     int cout, int cin, int cin_p, float* __restrict__ out) {
+  static_assert(PACKED ? G == 1 : G == 4, "the packed form adds the slabs in one chain, the OIHW form in four");
+  __shared__ float part[G][64];
+  const int64_t total = PACKED ? n * kpad : (int64_t)cout * cin * 9;
   const int e = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int64_t gid = (int64_t)blockIdx.x * 64 + e;
   const bool live = gid < total;
   // threads of a wave walk the PACKED row (coalesced reads of every slab); the OIHW element is computed from it
   const int64_t gi = live ? gid : 0;
-  const int o = (int)(gi / ((int64_t)cin * 9));
-  const int k = (int)(gi - (int64_t)o * cin * 9);               // k = tap * cin + c over the TRUE channels
-  const int tap = k / cin, c = k - tap * cin;
-  const int64_t stride = (int64_t)n * kpad;
-  const float* p = slabs + (int64_t)o * kpad + tap * cin_p + c + g * stride;
-  const int64_t step = RU_G * stride;
+  const int o = PACKED ? 0 : (int)(gi / ((int64_t)cin * 9));
+  const int k = PACKED ? 0 : (int)(gi - (int64_t)o * cin * 9);  // k = tap * cin + c over the TRUE channels
+  const int tap = PACKED ? 0 : k / cin, c = k - tap * cin;
+  const int64_t stride = n * kpad;
+  const float* p = slabs + (PACKED ? gi : (int64_t)o * kpad + tap * cin_p + c) + g * stride;
+  const int64_t step = G * stride;
   float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int m = g;
-  for (; m + 7 * RU_G < msplit; m += 8 * RU_G) {
+  for (; m + 7 * G < msplit; m += 8 * G) {
+    if (PACKED) {
+      float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) s[u] += p[(int64_t)u * step];
+      for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)u * step];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s[0] += v[u];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s[u] += p[(int64_t)u * step];
+    }
     p += 8 * step;
   }
-  for (; m < msplit; m += RU_G) {
+  for (; m < msplit; m += G) {
     s[0] += *p;
     p += step;
   }
+  if (PACKED) {
+    if (live) out[gid] = s[0];
+    return;
+  }
   part[g][e] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
   __syncthreads();
-  if (g == 0 && live) out[((int64_t)o * cin + c) * 9 + tap] = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
+  if (g == 0 && live) out[((int64_t)o * cin + c) * 9 + tap] = (part[0][e] + part[1 % G][e]) + (part[2 % G][e] + part[3 % G][e]);
 }
 
 }  // namespace ammc_s16
 using namespace ammc_s16;
+
+// out[e] = sum over s = 0 .. msplit-1, in that order, of slabs[s * total + e]   (e < total; ammc_common.h)
+int ammc_reduce_wgrad_slabs(const float* slabs, int msplit, int64_t total, float* out, hipStream_t stream) {
+  if (!slabs || !out || msplit <= 0 || total <= 0) return AMMC_EINVAL;
+  hipLaunchKernelGGL((reduce_unpack_wgrad_kernel<1, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream,
+                     slabs, msplit, (int64_t)1, total, 0, 0, 0, out);
+  return ammc_launch_status();
+}
 
 extern "C" int64_t ammc_conv_wgrad_s16_slab_floats(const AmmcWgradDesc* desc) {
   if (!desc || desc->ntaps != 9 || desc->a_step > 1 || desc->n <= 0 || (desc->n % 32) || desc->cin < 8 ||
@@ -579,8 +605,8 @@ static int wgrad_s16_slabs_dispatch(const AmmcWgradDesc* desc, const float* g_in
     return AMMC_OK;
   }
   const int64_t total = (int64_t)cout * cin * 9;
-  hipLaunchKernelGGL(reduce_unpack_wgrad_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64 * RU_G), 0, (hipStream_t)stream,
-                     slabs, msplit, d.n, kpad, cout, cin, d.cin, dw_oihw);
+  hipLaunchKernelGGL((reduce_unpack_wgrad_kernel<RU_G, false>), dim3((unsigned)((total + 63) / 64)), dim3(64 * RU_G), 0, (hipStream_t)stream,
+                     slabs, msplit, (int64_t)d.n, (int64_t)kpad, cout, cin, d.cin, dw_oihw);
   return ammc_launch_status();
 }
 

@@ -35,6 +35,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import ACT_LRELU, ACT_NONE, AmmcConvDesc, AmmcWgradDesc
 from .engine import Act, _cin_pad, _kpad, _ptr
+from .train import DETERMINISTIC, deterministic_of
 
 SLOPE = 0.1          # nn.LeakyReLU(0.1, True), pix2pix_networks.py:606
 HALO = 2             # = the convs' padding
@@ -113,6 +114,8 @@ class DiscEngine:
         self._grads16: Dict[Tuple[int, int, int], List[Act]] = {}
         self._scratch: Optional[torch.Tensor] = None
         self._zeros: Optional[torch.Tensor] = None
+        self._det_slabs: Dict[int, torch.Tensor] = {}     # `deterministic`: slab workspace of the weight gradients, per HIP stream
+        deterministic_of(module)                           # (refuses AMMC_WGRAD_TAP=2 with the switch on)
         self.slots_created = 0
 
     # ---- plumbing --------------------------------------------------------------------------------------------
@@ -128,6 +131,7 @@ class DiscEngine:
             self._grads16.clear()
             self._zeros = torch.zeros(1024, device=device)
             self._scratch = None
+            self._det_slabs.clear()
 
     def _take(self, B, H, W) -> Tuple[_Slot, list]:
         pool = self._pools.setdefault((B, H, W), [])
@@ -234,6 +238,15 @@ class DiscEngine:
         _chk(lib.ammc_reduce_partials_f32(_ptr(self._scratch), nb, c, 1.0, _ptr(out), self.s), "reduce_partials")
         return out
 
+    def _slab_ws(self, need: int) -> torch.Tensor:
+        """slab workspace of the deterministic weight gradients on the CURRENT HIP stream (launches of one stream use it
+        one after the other; D's two backward passes of a joint iteration may run on different streams)"""
+        key = self.s
+        ws = self._det_slabs.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._det_slabs[key] = torch.empty(max(need, 1 << 20), device=self.device, dtype=torch.float32)
+        return ws
+
     def backward(self, slot: _Slot, dout: torch.Tensor, need_dx: bool, need_dw: bool):
         lib, s, B = self.lib, self.s, slot.B
         gs = self._grad_acts(slot)
@@ -244,6 +257,7 @@ class DiscEngine:
              "dout->nhwc")
         grads: List[Optional[torch.Tensor]] = [None] * (2 * len(self.layers))
         dx = None
+        det = deterministic_of(self.module)
         for i in reversed(range(len(self.layers))):
             L, g, a = self.layers[i], gs[i], slot.acts[i]
             if i + 1 < len(self.layers):                                # LeakyReLU mask from the layer's own output
@@ -262,7 +276,8 @@ class DiscEngine:
                                                     1024, s), "split_rows_scaled(g)")
             if need_dw:
                 grads[2 * i + 1] = self._chan_sum(g, g.c if L.cout > 1 else 4)[:L.cout].clone()
-                dwp = torch.zeros(L.n, L.kpad, device=self.device)
+                # `deterministic`: the slab forms WRITE every element of dwp - nothing to zero
+                dwp = torch.empty(L.n, L.kpad, device=self.device) if det else torch.zeros(L.n, L.kpad, device=self.device)
                 d = AmmcWgradDesc()
                 d.dw, d.zeros = _ptr(dwp), _ptr(self._zeros)
                 d.batch, d.height, d.width = B, g.H, g.W
@@ -271,10 +286,18 @@ class DiscEngine:
                 d.a_bs, d.a_rs, d.a_ps = a.strides
                 if self.s16:                       # S16 twins of the gradient and of the layer input (written by the forward)
                     d.g, d.a = g16.pix0(), _ptr(slot.acts16[i].buf)
-                    _chk(lib.ammc_conv_wgrad_s16(C.byref(d), _ptr(inv), s), f"disc.wgrad{i}(s16)")
+                    if det:
+                        ws = self._slab_ws(int(lib.ammc_conv_wgrad_s16_det_floats(C.byref(d))))
+                        _chk(lib.ammc_conv_wgrad_s16_det(C.byref(d), _ptr(inv), _ptr(ws), ws.numel(), s), f"disc.wgrad{i}(s16, det)")
+                    else:
+                        _chk(lib.ammc_conv_wgrad_s16(C.byref(d), _ptr(inv), s), f"disc.wgrad{i}(s16)")
                 else:
                     d.g, d.a = g.pix0(), _ptr(a.buf)
-                    _chk(lib.ammc_conv_wgrad_f32(C.byref(d), s), f"disc.wgrad{i}")
+                    if det:
+                        ws = self._slab_ws(int(lib.ammc_conv_wgrad_f32_det_floats(C.byref(d))))
+                        _chk(lib.ammc_conv_wgrad_f32_det(C.byref(d), _ptr(ws), ws.numel(), s), f"disc.wgrad{i}(det)")
+                    else:
+                        _chk(lib.ammc_conv_wgrad_f32(C.byref(d), s), f"disc.wgrad{i}")
                 dw = torch.empty(L.cout, L.cin, 4, 4, device=self.device)
                 _chk(lib.ammc_unpack_conv_wgrad_f32(_ptr(dwp), L.cout, L.cin, 4, L.cin_p, _ptr(dw), s), "unpack_wgrad")
                 grads[2 * i] = dw
@@ -352,6 +375,7 @@ class PixelDiscriminator(nn.Module):
         net.append(nn.Conv2d(num_filters[-1], 1, 4, 1, 2))
         self.net = nn.Sequential(*net)                     # parameter holders; never called
         self.precision = DEFAULT_PRECISION
+        self.deterministic = DETERMINISTIC                 # AMMC_DETERMINISTIC: weight gradients without atomics (train.py)
         object.__setattr__(self, "_engine", None)
 
     def _params(self) -> List[torch.Tensor]:

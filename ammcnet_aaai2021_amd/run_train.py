@@ -76,7 +76,7 @@ import torch
 
 import torch.distributed as dist
 
-from . import harness, parallel, pipeline, synthetic
+from . import harness, parallel, pipeline, synthetic, train
 from .discriminator import PixelDiscriminator
 from .flownet import FlowNet2SD
 from .unet import get_twostream, get_unet_vq_topk_res
@@ -121,6 +121,10 @@ def parse(argv=None) -> argparse.Namespace:
     p.add_argument("--resume", action="store_true")
     p.add_argument("--precision", choices=("s16", "fp32"), default="s16",
                    help="training kernels of the generator, discriminator and flow network")
+    p.add_argument("--deterministic", action="store_true",
+                   help="bit-reproducible training (one rank): every weight gradient without atomics, in a fixed summation "
+                        "order (`model.deterministic` on the generator and the discriminator; also AMMC_DETERMINISTIC=1); "
+                        "recorded in the train state, and --resume refuses a run whose recorded flag differs")
     p.add_argument("--dist_backend", choices=("nccl", "gloo"), default="nccl",
                    help="process group of a multi-rank run: nccl (RCCL), or gloo so that ranks may share one GPU")
     p.add_argument("--sync_stats", action="store_true",
@@ -192,15 +196,30 @@ def build_models(a):
 def to_device(G, D, F2, a, dev):
     G = G.to(dev).train()
     G.train_precision = a.precision
+    G.deterministic = deterministic_on(a)
     if D is not None:
         D = D.to(dev).train()
         D.precision = a.precision
+        D.deterministic = deterministic_on(a)
     flow_fn = None
     if F2 is not None:
         F2 = F2.to(dev).eval()
         F2.precision = a.precision
         flow_fn = harness.flownet_flow_fn(F2)
     return G, D, flow_fn
+
+
+def deterministic_on(a) -> bool:
+    """--deterministic, or the process-wide default AMMC_DETERMINISTIC"""
+    return bool(a.deterministic or train.DETERMINISTIC)
+
+
+def check_resume_deterministic(state: dict, a) -> None:
+    """a deterministic run goes on deterministically and the other way round: the flag is part of what a run is"""
+    saved = bool(state.get("deterministic", False))
+    if saved != deterministic_on(a):
+        raise SystemExit(f"--resume: the train state was written {'with' if saved else 'without'} --deterministic and this "
+                         f"run is {'deterministic' if deterministic_on(a) else 'not'}: resume it as it was started")
 
 
 def _latest(folder: str):
@@ -299,6 +318,7 @@ def _train(a, dev, rank: int, world: int) -> dict:
         if D is not None:
             D.load_state_dict(torch.load(os.path.join(a.out, "discriminator", name), map_location="cpu"), strict=True)
         check_resume_batch(resumed, world, a.batch)
+        check_resume_deterministic(resumed, a)
         g_step = int(resumed["g_step"])
     G, D, flow_fn = to_device(G, D, F2, a, dev)
     nets = [m for m in (G, D) if m is not None]
@@ -361,6 +381,7 @@ def _train(a, dev, rank: int, world: int) -> dict:
             "bank_device_GB": round(bank.device_nbytes / 1e9, 6), "bank_host_GB": round(bank.host_nbytes / 1e9, 6), "prefetch": prefetch, "fill_seconds": round(bank.fill_seconds, 3),
             "workers": a.workers, "batch": a.batch, "world": world, "global_batch": world * a.batch, "size": a.size,
             "precision": a.precision, "fused_loss": bool(harness.FUSED_LOSS), "sync_stats": bool(a.sync_stats and world > 1),
+            "deterministic": deterministic_on(a),
             "flow_term": ("off: no --flownet" if flow_fn is None else f"on ({a.flownet})"), "resumed": resumed is not None}
     log_path = os.path.join(a.out, "train_log.jsonl")
 
@@ -451,7 +472,8 @@ def _train(a, dev, rank: int, world: int) -> dict:
                                  "the run has desynchronised - nothing was saved for this step")
             if rank == 0:
                 state = {"stage": a.stage, "g_step": g_step, "world": world, "opt_g": opt_g.state_dict(),
-                         "sched_g": sched_g.state_dict(), "sampler": state_before, "skipped": skipped, "args": args_rec}
+                         "sched_g": sched_g.state_dict(), "sampler": state_before, "skipped": skipped, "args": args_rec,
+                         "deterministic": deterministic_on(a)}
                 if D is not None:
                     state.update(opt_d=opt_d.state_dict(), sched_d=sched_d.state_dict())
                 save_all(a.out, G, D, state, g_step)

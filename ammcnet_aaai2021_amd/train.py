@@ -37,6 +37,22 @@ STAT_SEG = 128
 # HIP streams, so that one's HBM-bound BatchNorm passes (~1170 W at 6 TB/s) run beside the other's MFMA-bound convolutions
 # instead of after them: the step is energy-bound and those passes leave ~230 W of the 1400 W cap unused
 TWO_STREAMS = os.environ.get("AMMC_TWO_STREAMS", "1") != "0"
+# Deterministic training (opt-in): every weight gradient that would end in fp32 atomics - the implicit-GEMM kernels behind
+# ammc_conv_wgrad_s16 / ammc_conv_wgrad_f32 - takes its slab form (`_det` entries: plain stores + a fixed-order sum), so
+# one rank, one build, one device model, the same arguments and seed give the same bits (DESIGN.md "Deterministic
+# training").  Process-wide default; per model: `model.deterministic = True | False`, read at every step.
+DETERMINISTIC = os.environ.get("AMMC_DETERMINISTIC", "0") != "0"
+
+
+def deterministic_of(module) -> bool:
+    """the switch of `module` (`module.deterministic`; modules without the attribute follow AMMC_DETERMINISTIC), checked
+    against what the mode cannot keep: AMMC_WGRAD_TAP=2 selects a weight-gradient kernel that has only an atomics form"""
+    det = getattr(module, "deterministic", None)
+    det = DETERMINISTIC if det is None else bool(det)
+    if det and os.environ.get("AMMC_WGRAD_TAP", "") == "2":
+        raise RuntimeError("deterministic training: AMMC_WGRAD_TAP=2 selects wgrad_tap_s16, whose weight gradients end in "
+                           "fp32 atomics and have no deterministic form - unset AMMC_WGRAD_TAP or turn `deterministic` off")
+    return det
 
 
 class _WS:
@@ -111,6 +127,7 @@ class _Ops:
         self._shadows: Dict[int, torch.Tensor] = {}
         self.side = None                                   # two HIP streams of `_side_by_side`, made on first use
         self._wgrad_slabs: Dict[int, torch.Tensor] = {}    # slab workspace of the 3x3 weight gradients, per HIP stream
+        self.deterministic = False      # set per step by the engines (`deterministic_of(module)`): the `_det` weight gradients
         # bench.py: a list here brackets every MFMA launch of the 3x3 layers with HIP events on the launch stream and
         # collects (kernel label, algorithmic flops, start event, end event)
         self.timing: Optional[list] = None
@@ -201,20 +218,30 @@ class _Ops:
         if out_oihw is not None and ntaps == 9 and a_step == 1:
             need = int(self.lib.ammc_conv_wgrad_s16_slab_floats(C.byref(d)))
             if need > 0:
-                # one slab workspace per HIP stream (the rgb / flow halves of a step run on two): sized for the largest user
-                key = torch.cuda.current_stream(self.dev).cuda_stream
-                ws = self._wgrad_slabs.get(key)
-                if ws is None or ws.numel() < need:
-                    ws = self._wgrad_slabs[key] = torch.empty(max(need, 20 << 20), device=self.dev, dtype=torch.float32)
+                ws = self._slab_ws(need, 20 << 20)           # sized for the largest user
                 cout, cin_t = out_oihw.shape[0], out_oihw.shape[1]
                 self._mfma_launch(label, flops, lambda: self.lib.ammc_conv_wgrad_s16_slabs(
                     C.byref(d), _ptr(inv) if inv is not None else None, _ptr(ws), ws.numel(), _ptr(out_oihw), cout, cin_t, self.s), what)
                 return True
+        if self.deterministic:             # the im2col kernel's slab form: stores + a fixed-order sum that WRITES dw (no zeroing)
+            ws = self._slab_ws(int(self.lib.ammc_conv_wgrad_s16_det_floats(C.byref(d))), 1 << 20)
+            self._mfma_launch(label, flops, lambda: self.lib.ammc_conv_wgrad_s16_det(
+                C.byref(d), _ptr(inv) if inv is not None else None, _ptr(ws), ws.numel(), self.s), what)
+            return False
         if not getattr(dw, "_ammc_zslab", False):          # slab buffers were cleared by `_WS.zero_step` (backward start)
             dw.zero_()
         self._mfma_launch(label, flops,
                           lambda: self.lib.ammc_conv_wgrad_s16(C.byref(d), _ptr(inv) if inv is not None else None, self.s), what)
         return False
+
+    def _slab_ws(self, need: int, floor: int) -> torch.Tensor:
+        """the slab workspace of the CURRENT HIP stream (the rgb / flow halves of a step run on two; launches of one stream
+        use it one after the other), at least `need` floats, `floor` when it is first made"""
+        key = torch.cuda.current_stream(self.dev).cuda_stream
+        ws = self._wgrad_slabs.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._wgrad_slabs[key] = torch.empty(max(need, floor), device=self.dev, dtype=torch.float32)
+        return ws
 
     def conv_s16(self, x: Act, w: torch.Tensor, y: Act, *, ntaps, cin, n, res: Optional[Act] = None, what="conv",
                  pre=None, shift=None, up=1, cgroup=None, x_step=1, y_s16: bool = False,
@@ -306,7 +333,7 @@ class _Ops:
         _chk(self.lib.ammc_conv_gemm_f32(C.byref(d), self.s), what)
 
     def wgrad(self, g: Act, a: Act, dw: torch.Tensor, *, n, cin, ntaps, a_step=1, what="wgrad"):
-        if not getattr(dw, "_ammc_zslab", False):
+        if not self.deterministic and not getattr(dw, "_ammc_zslab", False):
             dw.zero_()
         d = AmmcWgradDesc()
         d.g = g.pix0()
@@ -316,6 +343,10 @@ class _Ops:
         d.n, d.cin, d.ntaps, d.a_step = n, cin, ntaps, a_step
         d.g_bs, d.g_rs, d.g_ps = g.strides
         d.a_bs, d.a_rs, d.a_ps = a.strides
+        if self.deterministic:             # slab form: stores + a fixed-order sum that WRITES dw
+            ws = self._slab_ws(int(self.lib.ammc_conv_wgrad_f32_det_floats(C.byref(d))), 1 << 20)
+            _chk(self.lib.ammc_conv_wgrad_f32_det(C.byref(d), _ptr(ws), ws.numel(), self.s), what)
+            return
         _chk(self.lib.ammc_conv_wgrad_f32(C.byref(d), self.s), what)
 
     def chan_sum(self, x: Act, c: int, scratch: torch.Tensor) -> torch.Tensor:
@@ -1000,6 +1031,7 @@ class TrainEngine:
         if precision not in ("fp32", "s16"):
             raise ValueError("train precision must be 'fp32' (exact fp32 MFMA) or 's16' (split-fp16 MFMA 3x3 layers)")
         self.module, self.kind, self.precision = module, kind, precision
+        deterministic_of(module)            # (refuses AMMC_WGRAD_TAP=2 with the switch on, before anything is allocated)
         self._ws: Dict = {}
         self.generation = 0
 
@@ -1041,6 +1073,7 @@ class TrainEngine:
         sync = getattr(self.module, "_sync_stats", None)          # parallel.sync_statistics(model, group)
         st["ops"].sync_group = sync[1] if sync and sync[0] else False
         st["ops"].sync_force = bool(sync and sync[0] and len(sync) > 2 and sync[2])
+        st["ops"].deterministic = deterministic_of(self.module)
         self.generation += 1
         st["generation"] = self.generation
         xs = [x.detach().float().contiguous() for x in inputs]
@@ -1160,11 +1193,15 @@ class BlockEngine:
     need >= 32 input channels (the input-gradient convolution's tiles); for thinner inputs - the 12 / 6-channel clips
     of `inconv` - the input gets no gradient, as data does not need one."""
 
-    def __init__(self, module, kind: str, precision: Optional[str] = None):
+    def __init__(self, module, kind: str, precision: Optional[str] = None, owner=None):
+        """`owner`: the module the user calls and configures (`inconv` around its `double_conv`): its `train_precision`
+        arrives as `precision`, its `deterministic` is read at every step"""
         precision = precision or TRAIN_PRECISION
         if kind not in ("double_conv", "down", "up", "bridge"):
             raise ValueError(kind)
         self.module, self.kind, self.precision = module, kind, precision
+        self.owner = owner if owner is not None else module
+        deterministic_of(self.owner)
         self._ws: Dict = {}
         self.generation = 0
 
@@ -1234,6 +1271,7 @@ class BlockEngine:
         st = self._get(tuple(tuple(x.shape) for x in inputs), inputs[0].device)
         ops, lib = st["ops"], st["ops"].lib
         ops.sync_group = False
+        ops.deterministic = deterministic_of(self.owner)
         self.generation += 1
         st["generation"] = self.generation
         self._last = st
@@ -1318,10 +1356,13 @@ class MemoryBlockEngine:
     (`ammc_commit_bwd_f32`), the weight / bias / input gradients of the two 1x1 convolutions.  The gathered rows
     (`quantize_topk`) come out of a buffer: no gradient reaches anything through them, exactly as in the reference."""
 
-    def __init__(self, module, kind: str, precision: Optional[str] = None):
+    def __init__(self, module, kind: str, precision: Optional[str] = None, owner=None):
+        """`owner`: the module the user calls (`enc_quan_dec_res_topk` around its `quan`): its `deterministic` is read"""
         if kind not in ("quantize", "vq", "vq_res"):
             raise ValueError(kind)
         self.module, self.kind = module, kind
+        self.owner = owner if owner is not None else module
+        deterministic_of(self.owner)
         self.precision = "fp32"                     # 1x1 convolutions and the lookups run on the exact-fp32 kernels
         self._ws: Dict = {}
         self.generation = 0
@@ -1367,6 +1408,7 @@ class MemoryBlockEngine:
         st = self._get(tuple(x.shape), x.device)
         o, lib = st["ops"], st["ops"].lib
         o.sync_group = False
+        o.deterministic = deterministic_of(self.owner)
         s = o.s
         self.generation += 1
         st["generation"] = self.generation

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import EvalEngine
-from .train import BlockEngine, BlockFunction, HipPathFunction, MemoryBlockEngine, MemoryBlockFunction, TrainEngine
+from .train import DETERMINISTIC, BlockEngine, BlockFunction, HipPathFunction, MemoryBlockEngine, MemoryBlockFunction, TrainEngine
 
 
 # Inference arithmetic: "s16" (default) = split-fp16 MFMA with fp32 accumulation: 22 significant bits per operand,
@@ -37,13 +37,13 @@ DEFAULT_PRECISION = os.environ.get("AMMC_PRECISION", "s16")
 DEFAULT_S16_GUARD = True
 
 
-def _run_memory(mod, kind: str, x):
+def _run_memory(mod, kind: str, x, owner=None):
     """training-mode forward of the memory block on its own (`Quantize_topk`, `enc_quan_dec_topk`,
     `enc_quan_dec_res_topk`): one autograd node over the HIP kernels; the EMA buffers are updated in place as the
     reference does whenever `self.training` (models/unet.py:298-309)"""
     eng = mod.__dict__.get("_block_engine")
     if eng is None or eng.kind != kind:
-        eng = MemoryBlockEngine(mod, kind)
+        eng = MemoryBlockEngine(mod, kind, owner=owner)       # (`owner.deterministic`: the module the user calls)
         object.__setattr__(mod, "_block_engine", eng)
     return MemoryBlockFunction.apply(eng, x, *mod.parameters())
 
@@ -53,7 +53,7 @@ def _run_block(mod, kind: str, owner, *inputs):
     eng = owner.__dict__.get("_block_engine")
     tprec = getattr(owner, "train_precision", None)
     if eng is None or (tprec is not None and eng.precision != tprec):
-        eng = BlockEngine(mod, kind, tprec)
+        eng = BlockEngine(mod, kind, tprec, owner=owner)
         object.__setattr__(owner, "_block_engine", eng)
     return BlockFunction.apply(eng, len(inputs), *inputs, *mod.parameters())
 
@@ -153,6 +153,7 @@ class UNet(nn.Module):
         self.outc = nn.Conv2d(64, output_channel, kernel_size=3, padding=1)
         self._engine = self._train_engine = None
         self._param_epoch = 0
+        self.deterministic = DETERMINISTIC      # AMMC_DETERMINISTIC: weight gradients without atomics (train.py), read every step
 
     def forward(self, x):
         out = _run(self, "unet", 1, x)
@@ -203,7 +204,7 @@ class enc_quan_dec_res_topk(nn.Module):
 
     def forward(self, x):
         if self.training:
-            return _run_memory(self.quan, "vq_res", x)
+            return _run_memory(self.quan, "vq_res", x, owner=self)
         return ops.vq_block_eval(self.quan, x, residual=True)
 
 
@@ -222,6 +223,7 @@ class UNetMem_v7(nn.Module):
         self.vq_down3 = enc_quan_dec_res_topk(512, embed_dim, n_embed, k=k)
         self._engine = self._train_engine = None
         self._param_epoch = 0
+        self.deterministic = DETERMINISTIC      # AMMC_DETERMINISTIC: weight gradients without atomics (train.py), read every step
 
     def forward(self, x):
         return _run(self, "unetmem", 1, x)
@@ -251,6 +253,7 @@ class twostream(nn.Module):
         self.bridge = bridge(in_c=512)
         self._engine = self._train_engine = None
         self._param_epoch = 0
+        self.deterministic = DETERMINISTIC      # AMMC_DETERMINISTIC: weight gradients without atomics (train.py), read every step
 
     def forward(self, rgb_x, op_x):
         out = _run(self, "twostream", 2, rgb_x, op_x)

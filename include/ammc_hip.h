@@ -374,6 +374,30 @@ int ammc_conv_wgrad_s16_slabs(const AmmcWgradDesc* desc, const float* g_inv_scal
  * the slab entry has no kernel for the descriptor (slab_floats == 0), AMMC_EINVAL as that entry.  out_len >= 64. */
 int ammc_conv_wgrad_s16_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len);
 int ammc_conv_wgrad_s16_slabs_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len);
+/* Deterministic forms of the two implicit-GEMM weight-gradient kernels (wgrad_s16_kernel / wgrad_f32_kernel): the same
+ * operands, the same pixel splits and the same packed result desc->dw [n][kpad] as ammc_conv_wgrad_s16 /
+ * ammc_conv_wgrad_f32 (ammc_unpack_conv_wgrad_f32 / ammc_unpack_convt_wgrad_f32 follow as before), but no atomic: every
+ * workgroup stores its tile into the slab of its pixel split (slabs: [k][n][kpad] floats of caller workspace, plain
+ * stores; nothing of it needs initialising) and a second kernel writes dw[r][c] = slab 0 [r][c] + slab 1 [r][c] + ... +
+ * slab k-1 [r][c], added in that order.  dw needs NO zeroing: every element [n][kpad] is written (the S16 form writes the
+ * columns ntaps * cin .. kpad as zeros).  Equal operands give equal bits, whatever else the device runs.
+ *   ammc_conv_wgrad_*_det_floats: the workspace, k * n * kpad floats, k = the pixel splits - a function of the descriptor
+ *     alone (shape, n, cin, ntaps; no device query, no environment switch, no launch history).  0 where the descriptor
+ *     is refused and where k == 1: the one workgroup per tile then stores straight into dw and `slabs` may be NULL.
+ *   ammc_conv_wgrad_s16_det runs wgrad_s16_kernel for EVERY descriptor ammc_conv_wgrad_s16's checks accept - the
+ *     halo-patch dispatchers and their switches (AMMC_WGRAD_TAP, ...) are not asked; the stride-1 3x3 layers that have a
+ *     slab form are better served by ammc_conv_wgrad_s16_slabs, which is deterministic too.
+ *   Status codes: those of the atomics entry for the same descriptor; AMMC_EINVAL when k > 1 and slabs is NULL or
+ *     slab_floats is short.
+ *   ammc_conv_wgrad_*_det_variant: nothing is launched, no HIP call, the same checks (all four pointers included); the
+ *     kernel's name + "+det<k>" ("wgrad_s16+det3", "wgrad_f32<1, 4, 2, 1>+det12").  out_len >= 48. */
+int64_t ammc_conv_wgrad_s16_det_floats(const AmmcWgradDesc* desc);
+int ammc_conv_wgrad_s16_det(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs, int64_t slab_floats,
+                            void* stream);
+int ammc_conv_wgrad_s16_det_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len);
+int64_t ammc_conv_wgrad_f32_det_floats(const AmmcWgradDesc* desc);
+int ammc_conv_wgrad_f32_det(const AmmcWgradDesc* desc, float* slabs, int64_t slab_floats, void* stream);
+int ammc_conv_wgrad_f32_det_variant(const AmmcWgradDesc* desc, char* out, int32_t out_len);
 /* packed gradient -> the module's parameter layout */
 int ammc_unpack_conv_wgrad_f32(const float* packed, int32_t cout, int32_t cin, int32_t ksize, int32_t cin_p,
                                float* out_oihw, void* stream);
