@@ -175,6 +175,8 @@ SIGNATURES = {
     "ammc_pred_loss_fwd_f32": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "ammc_pred_loss_bwd_f32": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "ammc_l1_partials_f32": (C.c_int, [_p, _p, _i64, _p, _p]),
+    "ammc_error_maps_patch_count": (C.c_int, [_i32, _i32, _i32]),
+    "ammc_error_maps_f32": (C.c_int, [_p] + _s3 + [_p] + _s3 + [_i32] * 5 + [_p, _i64, _p, _p, _i64, _p, _p, _p, _p]),
 }
 
 _lib = None

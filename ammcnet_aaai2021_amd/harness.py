@@ -242,6 +242,182 @@ class _Done:
         pass
 
 
+# ---- anomaly localisation: patch / pixel error maps and the fixed-order PSNR --------------
+# A pass of its own behind the evaluation forward (`ops.error_maps`, csrc/error_maps.hip): the scoring loops above and the
+# fused epilogue sums they read are not touched.
+
+def error_maps_reference(pred: torch.Tensor, target: torch.Tensor, patch: int) -> Dict[str, torch.Tensor]:
+    """the quantities of `ops.error_maps` in float64 with plain torch (any device; the reference of the tests): with
+    e = (target - pred) / 2, `pixel` [B,H,W] = mean_c e^2, `patch_sum` / `patch_mean` [B,ph,pw] over patch x patch pixels
+    anchored at (0, 0) (the last patch row / column ragged, means over the pixels that exist), `frame_sq` [B] = the sum of
+    the patch sums, `worst` / `worst_idx` [B] = the largest patch mean and the lowest i * pw + j attaining it,
+    `psnr` = 10 log10(C H W / frame_sq)"""
+    b, c, h, w = pred.shape
+    sq = ((target.double() - pred.double()) * 0.5) ** 2
+    per_px = sq.sum(1)                                                      # [B,H,W], summed over channels
+    ph, pw = (h + patch - 1) // patch, (w + patch - 1) // patch
+    padded = torch.zeros((b, ph * patch, pw * patch), dtype=torch.float64, device=pred.device)
+    padded[:, :h, :w] = per_px
+    patch_sum = padded.view(b, ph, patch, pw, patch).sum(dim=(2, 4))
+    rows = torch.clamp(h - torch.arange(ph, device=pred.device) * patch, max=patch)
+    cols = torch.clamp(w - torch.arange(pw, device=pred.device) * patch, max=patch)
+    count = (c * rows[:, None] * cols[None, :]).double()
+    patch_mean = patch_sum / count
+    frame_sq = patch_sum.sum(dim=(1, 2))
+    flat = patch_mean.reshape(b, -1)
+    worst = flat.max(dim=1).values
+    first = (flat == worst[:, None]).int().argmax(dim=1)                     # argmax of 0/1: the first maximum
+    return {"pixel": per_px / c, "patch_sum": patch_sum, "patch_mean": patch_mean, "frame_sq": frame_sq, "worst": worst,
+            "worst_idx": first.to(torch.int32), "psnr": 10.0 * torch.log10(float(c * h * w) / frame_sq)}
+
+
+def assemble_localised(n_frames: int, batches, parts: Sequence[Dict[str, np.ndarray]]) -> Dict[str, np.ndarray]:
+    """per-frame arrays of one sub-video from its batches' outputs, with the frame indexing and the fills of
+    `assemble_records`: clip i of a batch fills frame i + len_clip - 1 of its stream, a per-batch scalar (`*_comm`) every
+    frame of the batch, the first len_clip - 1 frames copy frame len_clip - 1, and the flow stream's last frame copies
+    the one before it.  parts[k]: {"rgb_psnr": [b], "rgb_patch": [b, ph, pw], "rgb_comm": scalar, "op_...": ...}"""
+    rec: Dict[str, np.ndarray] = {}
+    for key, v0 in parts[0].items():
+        v0 = np.asarray(v0)
+        lc = RGB_LEN_CLIP if key.startswith("rgb_") else OP_LEN_CLIP
+        per_clip = v0.ndim > 0
+        out = np.empty((n_frames,) + (v0.shape[1:] if per_clip else ()), dtype=v0.dtype)
+        for (s, e), part in zip(batches, parts):
+            out[s + lc - 1:e + lc - 1] = np.asarray(part[key])
+        out[:lc - 1] = out[lc - 1]
+        if key.startswith("op_"):
+            out[n_frames - 1] = out[n_frames - 2]
+        rec[key] = out
+    return rec
+
+
+class _Slots:
+    """one flat fp32 device buffer per sub-video, carved into the per-clip outputs of both streams (a batch writes
+    straight into its clips' rows through `ops.error_maps(out=...)`) and the per-batch commit values and range flags: the
+    whole sub-video comes to the host by ONE copy"""
+
+    def __init__(self, n_clip: int, n_batch: int, shapes, patch: int, pixel: bool, device):
+        self.layout, off = {}, 0
+
+        def carve(name, shape):
+            nonlocal off
+            n = int(np.prod(shape))
+            self.layout[name] = (off, shape)
+            off += (n + 3) // 4 * 4                                         # sections start 16-byte aligned
+        for st, (_, h, w) in zip(("rgb", "op"), shapes):
+            ph, pw = (h + patch - 1) // patch, (w + patch - 1) // patch
+            carve(f"{st}_patch", (n_clip, ph, pw))
+            carve(f"{st}_patch_sum", (n_clip, ph, pw))
+            for k in ("frame_sq", "psnr", "worst", "worst_idx"):
+                carve(f"{st}_{k}", (n_clip,))
+            if pixel:
+                carve(f"{st}_pixel", (n_clip, h, w))
+        carve("comm", (n_batch, 2))
+        carve("flag", (n_batch,))
+        self.flat = torch.zeros(off, device=device, dtype=torch.float32)
+
+    def view(self, name: str, flat=None):
+        off, shape = self.layout[name]
+        v = (self.flat if flat is None else flat)[off:off + int(np.prod(shape))]
+        if name.endswith("_worst_idx"):
+            v = v.view(torch.int32) if isinstance(v, torch.Tensor) else v.view(np.int32)
+        return v.reshape(shape)
+
+
+def localise_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, patch: int = 16, pixel: bool = False,
+                      batch: int = EVAL_BATCH, predictions: Optional[list] = None) -> Dict[str, np.ndarray]:
+    """Where the anomaly is: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and on the model's device ->
+    per-frame numpy arrays of the sub-video: `rgb_patch` / `op_patch` [T,ph,pw] (patch means of the squared [0,1]-range
+    error), `rgb_psnr` / `op_psnr` (from the fixed-order sum: the same bits for the same predictions), `rgb_worst` /
+    `op_worst` (the largest patch mean), `rgb_worst_idx` / `op_worst_idx` (its i * pw + j), `rgb_comm` / `op_comm` [T],
+    and with `pixel` `rgb_pixel` / `op_pixel` [T,H,W].  Clips, targets and batches are those of `score_batch_device`
+    (`batch` clips at a time), the forward is the model's evaluation forward, frame indexing and fills are
+    `assemble_records`' (`assemble_localised`).  Every batch is queued back to back; one device-to-host copy per
+    sub-video; a batch whose S16 range flag is set is re-run with `exact=True`, as `score_batch` does.
+    `predictions`: a testing and cross-check hook, not part of the scoring - an optional list that receives
+    (s, e, rgb_pred, op_pred, fused) of every batch as scored (it keeps every batch's predicted frames alive); `fused` = the
+    [rgb, op] PSNR of the output layer's epilogue from the same forward."""
+    from . import ops
+    t = rgb_frames.shape[0]
+    if op_frames.shape[0] != t - 1:
+        raise ValueError("a sub-video of T frames has T-1 flows")
+    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
+        raise ValueError("localise_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
+    batches = subvideo_batches(t, batch)
+    if not batches:
+        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
+    n_clip = batches[-1][1]
+    slots = _Slots(n_clip, len(batches), (rgb_frames.shape[1:], op_frames.shape[1:]), patch, pixel, rgb_frames.device)
+
+    def run(k: int, exact: bool):
+        s, e = batches[k]
+        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
+        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
+        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        with torch.no_grad():
+            (rgb_out, op_out, diffs, _), *fused = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
+            flag = getattr(model, "last_overflow", None)
+            for st, pred, tgt in (("rgb", rgb_out, targets[0]), ("op", op_out, targets[1])):
+                out = {"patch_mean": slots.view(f"{st}_patch")[s:e], "patch_sum": slots.view(f"{st}_patch_sum")[s:e]}
+                for key in ("frame_sq", "worst", "worst_idx") + (("pixel",) if pixel else ()):
+                    out[key] = slots.view(f"{st}_{key}")[s:e]
+                slots.view(f"{st}_psnr")[s:e] = ops.error_maps(pred, tgt, patch, pixel, out)["psnr"]
+            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
+            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
+        return (s, e, rgb_out, op_out, fused) if predictions is not None else None      # (else the frames are let go)
+
+    done = [run(k, False) for k in range(len(batches))]
+    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
+    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
+    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
+        for k in flagged:
+            done[k] = run(k, True)
+            _count_fallback(model)
+        host = slots.flat.cpu().numpy()
+    if predictions is not None:
+        predictions.extend(done)
+    parts = []
+    for k, (s, e) in enumerate(batches):
+        part = {}
+        for st in ("rgb", "op"):
+            for key in ("patch", "psnr", "worst", "worst_idx") + (("pixel",) if pixel else ()):
+                part[f"{st}_{key}"] = slots.view(f"{st}_{key}", host)[s:e]
+        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
+        parts.append(part)
+    return assemble_localised(t, batches, parts)
+
+
+def evaluate_dataset_localised(model, videos, dataset_name: str = "synthetic", patch: int = 16, pixel: bool = False,
+                               maps_dir: Optional[str] = None, device=None) -> dict:
+    """`evaluate_dataset` with `localise_subvideo` in place of the scoring loop (one rank).  `videos`: a sequence of
+    (rgb_frames, op_frames) - host tensors are moved to `device` (default: the model's) one sub-video at a time - or an
+    iterator of device-resident sub-videos (`pipeline.SubVideoStager`).  Returns the four record lists of the
+    reference with `*_img_pred_records` from the fixed-order PSNR, plus `rgb_patch_psnr_records` (10 log10(1 / worst
+    patch mean) per frame: the worst-patch frame score, a drop-in for `rgb_img_pred_records` in `fuse_scores_auc`) and
+    `n_frames`.  `maps_dir`: one `NNNN.npz` per sub-video with the arrays of `localise_subvideo` (`map_files`)."""
+    if device is None:
+        device = next(model.parameters()).device
+    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
+           "op_fea_comm_records": [], "rgb_patch_psnr_records": [], "n_frames": [], "map_files": []}
+    if maps_dir:
+        os.makedirs(maps_dir, exist_ok=True)
+    for v, (rgb, op) in enumerate(videos):
+        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+        rec = localise_subvideo(model, rgb, op, patch, pixel)
+        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
+        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
+        out["op_img_pred_records"].append(rec["op_psnr"])
+        out["op_fea_comm_records"].append(rec["op_comm"])
+        with np.errstate(divide="ignore"):
+            out["rgb_patch_psnr_records"].append((10.0 * np.log10(1.0 / rec["rgb_worst"].astype(np.float64))).astype(np.float32))
+        out["n_frames"].append(int(rgb.shape[0]))
+        if maps_dir:
+            path = os.path.join(maps_dir, f"{v:04d}.npz")
+            np.savez(path, **rec)
+            out["map_files"].append(path)
+    return out
+
+
 # AMMC_FUSED_LOSS: 1 = the per-pixel terms of the generator's objective (intensity, gradient difference, flow) come from the
 # library's loss kernels (`losses.py`: one forward and one backward launch per prediction pair), 0 (default) = the torch
 # chains below.  Device tensors only: on the CPU the flag changes nothing.  profiles/loss_ab.txt holds the A/B.

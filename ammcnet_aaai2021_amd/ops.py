@@ -146,6 +146,80 @@ def vq_block_eval(quan, x: torch.Tensor, residual: bool):
     return y, diff, q1
 
 
+ERROR_MAP_PATCHES = (8, 16, 32)
+
+
+def _nchw_strides(t: torch.Tensor):
+    """(batch, channel, row) strides of an NCHW view for `ammc_error_maps_f32`; a dimension of size 1 may carry any
+    stride in torch - it is given the extent below it instead"""
+    _, c, h, w = t.shape
+    bs, cs, rs, _ = t.stride()
+    if h == 1:
+        rs = max(rs, w)
+    plane = (h - 1) * rs + w
+    if c == 1:
+        cs = max(cs, plane)
+    if t.shape[0] == 1:
+        bs = max(bs, (c - 1) * cs + plane)
+    return bs, cs, rs
+
+
+def error_maps(pred: torch.Tensor, target: torch.Tensor, patch: int = 16, pixel: bool = False, out: dict | None = None) -> dict:
+    """Where the prediction error sits (csrc/error_maps.hip; definitions in include/ammc_hip.h): `pred`, `target` fp32
+    [B, C, H, W] on the GPU, pixel stride 1, any batch / channel / row strides (nothing is copied).  Returns
+    `patch_sum`, `patch_mean` [B, ph, pw], `frame_sq`, `worst` [B], `worst_idx` [B] int32, `pixel` [B, H, W] when asked,
+    and `psnr` = 10 log10(C H W / frame_sq) as `EvalEngine.forward` forms it.  Two launches on torch's current stream;
+    every sum is taken in a fixed order, so equal inputs give equal bits.  `out`: tensors to write into, by the same
+    keys (views of per-sub-video buffers: a batch then fills its frames' slots) - maps with contiguous rows and
+    columns, any batch stride."""
+    _need_cuda(pred)
+    _need_cuda(target)
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"error_maps: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be equal [B, C, H, W] shapes")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32 or pred.device != target.device:
+        raise ValueError("error_maps: fp32 tensors on one device")
+    if pred.stride(3) != 1 or target.stride(3) != 1:
+        raise ValueError("error_maps: pixel stride 1 (NCHW views; make channels-last tensors contiguous first)")
+    if patch not in ERROR_MAP_PATCHES:
+        raise ValueError(f"error_maps: patch must be one of {ERROR_MAP_PATCHES}")
+    lib = _lib.load()
+    B, C, H, W = pred.shape
+    ph, pw = (H + patch - 1) // patch, (W + patch - 1) // patch
+    dev = pred.device
+    out = dict(out) if out else {}
+    want = {"patch_sum": ((B, ph, pw), torch.float32), "patch_mean": ((B, ph, pw), torch.float32),
+            "frame_sq": ((B,), torch.float32), "worst": ((B,), torch.float32), "worst_idx": ((B,), torch.int32)}
+    if pixel:
+        want["pixel"] = ((B, H, W), torch.float32)
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"error_maps: `out` has no slot {sorted(unknown)}")
+    res = {}
+    for key, (shape, dtype) in want.items():
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise ValueError(f"error_maps: out[{key!r}] must be {dtype} {shape} on {dev}")
+        elif t.dim() == 1 and B > 1 and t.stride(0) != 1:
+            raise ValueError(f"error_maps: out[{key!r}] must be contiguous")
+        elif t.dim() == 3 and not t[0].is_contiguous():
+            raise ValueError(f"error_maps: out[{key!r}]: the map of a sample must be contiguous (any batch stride)")
+        res[key] = t
+    ps, pm = res["patch_sum"], res["patch_mean"]
+    ps_bs = max(ps.stride(0), ph * pw) if B == 1 else ps.stride(0)
+    if B > 1 and pm.stride(0) != ps_bs:
+        raise ValueError("error_maps: out['patch_sum'] and out['patch_mean'] must share one batch stride")
+    px = res.get("pixel")
+    px_bs = 0 if px is None else (max(px.stride(0), H * W) if B == 1 else px.stride(0))
+    _lib.check(lib.ammc_error_maps_f32(_ptr(pred), *_nchw_strides(pred), _ptr(target), *_nchw_strides(target), B, C, H, W, patch,
+                                       _ptr(ps), ps_bs, _ptr(pm), _ptr(px) if px is not None else None, px_bs,
+                                       _ptr(res["frame_sq"]), _ptr(res["worst"]), res["worst_idx"].data_ptr(), _stream(pred)),
+               "error_maps")
+    res["psnr"] = 10.0 * torch.log10(float(C * H * W) / res["frame_sq"])
+    return res
+
+
 def embed_rows(embed: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     """`Quantize_topk.embed_code` (unet.py:315-316): rows of the transposed codebook"""
     return embed.t()[ids]

@@ -681,6 +681,40 @@ int ammc_pred_loss_bwd_f32(const float* pred, const float* target, int64_t targe
  * combine with ammc_sum_partials_f32(partial, n, 1 / count, out). */
 int ammc_l1_partials_f32(const float* a, const float* b, int64_t count, float* partial, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Anomaly localisation (csrc/error_maps.hip): per-patch and per-pixel squared-error maps of a predicted frame against
+ * its target, the frame's squared error summed in a fixed order, and the worst patch.  pred / target: fp32
+ * [batch][c][h][w] views, pixel stride 1, batch / channel / row strides in floats (the targets of a batch are a slice of
+ * a resident sub-video).  With e = 0.5f * (target - pred), the reference's `psnr_error` on [0, 1] (utils/utils.py:143-147):
+ *   pixel[b][y][x]      mean over the channels of e^2   (optional: pixel may be NULL; rows w floats apart, samples px_bs)
+ *   patch_sum[b][i][j]  sum of e^2 over the channels and pixels of patch (i, j): patch x patch pixels anchored at (0, 0),
+ *                       the last patch row / column ragged (only the pixels that exist); ph = ceil(h / patch),
+ *                       pw = ceil(w / patch), rows pw floats apart, samples ps_bs floats apart
+ *   patch_mean[b][i][j] patch_sum / (c * rows * cols) with the patch's true pixel count (same shape and strides)
+ *   frame_sq[b]         for each patch row i a double adds (double)patch_sum[b][i][0], [1], ... in that order; a second
+ *                       double adds those row values for i = 0, 1, ...; rounded once to fp32.
+ *                       PSNR = 10 log10(c h w / frame_sq)
+ *   worst[b]            the largest patch_mean[b] (one of the stored values, bit for bit)
+ *   worst_idx[b]        i * pw + j of that patch, the lowest index among equal values
+ * Two launches, no atomics, no allocation, no synchronisation: the same bits on every launch, and the order in which a
+ * patch's terms are added depends on (c, rows, cols, patch) of that patch only - not on the sample's place in the
+ * batch, the batch size, the strides or the alignment (16-byte loads where all bases and strides allow, 4-byte loads
+ * otherwise; both add in one order).  Non-finite inputs propagate into patch_sum, patch_mean, pixel and frame_sq;
+ * worst and worst_idx are UNSPECIFIED for a sample whose patch means hold a NaN.
+ * AMMC_EINVAL: a null pointer other than pixel; batch, c, h or w <= 0; pointers not 4-byte aligned; a row stride < w;
+ * a channel / batch stride smaller than the extent below it; ps_bs < ph * pw; px_bs < h * w with pixel given.
+ * AMMC_EUNSUP: c > 4; patch not 8, 16 or 32; batch * ph or ph * pw >= 2^31; a frame so wide that its quads (4 pixels)
+ * need more than 65535 column chunks of 64 (patch 8) or 32 (patch 16, 32) quads on the grid's y dimension, i.e.
+ * w > 16776960 resp. 8388480 (element offsets are 64-bit).
+ * All of them are decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+/* ceil(h / patch) * ceil(w / patch); 0 for bad arguments */
+int ammc_error_maps_patch_count(int32_t h, int32_t w, int32_t patch);
+int ammc_error_maps_f32(const float* pred, int64_t p_bs, int64_t p_cs, int64_t p_rs, const float* target, int64_t t_bs,
+                        int64_t t_cs, int64_t t_rs, int32_t batch, int32_t c, int32_t h, int32_t w, int32_t patch,
+                        float* patch_sum, int64_t ps_bs, float* patch_mean, float* pixel, int64_t px_bs, float* frame_sq,
+                        float* worst, int32_t* worst_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
