@@ -177,6 +177,7 @@ SIGNATURES = {
     "ammc_l1_partials_f32": (C.c_int, [_p, _p, _i64, _p, _p]),
     "ammc_error_maps_patch_count": (C.c_int, [_i32, _i32, _i32]),
     "ammc_error_maps_f32": (C.c_int, [_p] + _s3 + [_p] + _s3 + [_i32] * 5 + [_p, _i64, _p, _p, _i64, _p, _p, _p, _p]),
+    "ammc_memory_scores_f32": (C.c_int, [_p] + _s3 + [_i32] * 4 + [_p] * 5 + [_i32] * 3 + [_p, _i64, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

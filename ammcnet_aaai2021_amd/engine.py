@@ -725,6 +725,19 @@ class EvalEngine:
         s = self._last["streams"][0]
         return self.act_nchw(s.x4), self.act_nchw(s.x4q)
 
+    def bottleneck_inputs(self):
+        """the last forward's bottleneck in front of the memory block (`x4`) of EVERY stream as fp32 NHWC tensors
+        [B, h, w, 512] - what `ops.memory_scores` reads.  fp32 plans: the workspace's interior views; S16 plans: decoded
+        copies (hi + lo * 2^-11 fits fp32: the decode is exact).  Valid until the next forward of the same shape."""
+        out = []
+        for s in self._last["streams"]:
+            a = s.x4
+            if not self.s16 or a.halo == 0:
+                out.append(a.interior())
+            else:
+                out.append(self.act_nchw(a).permute(0, 2, 3, 1).contiguous())
+        return tuple(out)
+
     def overflowed(self, reset: bool = True) -> bool:
         """did an S16 activation of the last forward leave the half range?  (one device sync)"""
         flag = self._last.get("overflow")

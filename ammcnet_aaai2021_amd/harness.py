@@ -418,6 +418,165 @@ def evaluate_dataset_localised(model, videos, dataset_name: str = "synthetic", p
     return out
 
 
+# ---- per-clip memory-commit scores and maps -------------------------------------------------
+# A pass of its own behind the evaluation forward (`ops.memory_scores`, csrc/memory_scores.hip) over the bottleneck in
+# front of each stream's memory block: the scoring loops above, the fused memory block and its one `diff` scalar per
+# batch are not touched.
+
+def memory_scores_reference(enc_w: torch.Tensor, enc_b: torch.Tensor, embed: torch.Tensor, x: torch.Tensor,
+                            k: int) -> Dict[str, torch.Tensor]:
+    """the quantities of `ops.memory_scores` in float64 with plain torch (any device; the reference of the tests).
+    enc_w [d, c] (or [d, c, 1, 1]), enc_b [d], embed [d, m], x NHWC [B, h, w, c].  z = x enc_w^T + enc_b [B,h,w,d];
+    dist = |z|^2 - 2 z E + |E|^2 (models/unet.py:284-288); `idx` [B,h,w,k] = the k nearest slots, nearest first, equal
+    distances in ascending slot order; `map` [B,h,w] = sum_j (E[j][idx0] - z[j])^2 / d taken directly; `commit` [B] = the
+    mean of `map`; `worst` / `worst_idx` [B] = the largest map value and the lowest y * w + x attaining it.  For the
+    tests also `z`, `dist` [B,h,w,m], `order` [B,h,w,min(k+1,m)] (the first slots of the stable sort), `margin` [B,h,w] =
+    the smallest gap between consecutive sorted distances among those (inf when there is one), `znorm` = |z|^2 and
+    `scale` = (|z|^2 + |E[:, idx0]|^2) / d, what the rounding error of a map entry is proportional to."""
+    d, m = embed.shape
+    e = embed.double()
+    z = x.double() @ enc_w.double().reshape(d, -1).t() + enc_b.double()
+    b, h, w, _ = z.shape
+    znorm = (z * z).sum(-1)
+    dist = znorm[..., None] - 2.0 * (z @ e) + (e * e).sum(0)
+    srt, order = torch.sort(dist, dim=-1, stable=True)
+    n = min(k + 1, m)
+    idx = order[..., :k]
+    near = e.t()[idx[..., 0]]                                                  # [B,h,w,d]
+    s = ((near - z) ** 2).sum(-1)
+    mp = s / d
+    gaps = srt[..., 1:n] - srt[..., :n - 1]
+    margin = gaps.min(-1).values if n > 1 else torch.full_like(mp, float("inf"))
+    flat = mp.reshape(b, -1)
+    worst = flat.max(dim=1).values
+    first = (flat == worst[:, None]).int().argmax(dim=1)                       # argmax of 0/1: the first maximum
+    return {"z": z, "idx": idx.to(torch.int32), "map": mp, "commit": flat.mean(dim=1), "worst": worst,
+            "worst_idx": first.to(torch.int32), "dist": dist, "order": order[..., :n], "margin": margin, "znorm": znorm,
+            "scale": (znorm + (near * near).sum(-1)) / d}
+
+
+class _FlatSlots:
+    """one flat 4-byte device buffer per sub-video carved into named sections (fp32, or int32 for the names in
+    `ints`): batches write straight into their clips' rows and the whole sub-video comes to the host by ONE copy"""
+
+    def __init__(self, sections, ints, device):
+        self.layout, self.ints, off = {}, set(ints), 0
+        for name, shape in sections:
+            self.layout[name] = (off, tuple(shape))
+            off += (int(np.prod(shape)) + 3) // 4 * 4                          # sections start 16-byte aligned
+        self.flat = torch.zeros(off, device=device, dtype=torch.float32)
+
+    def view(self, name: str, flat=None):
+        off, shape = self.layout[name]
+        v = (self.flat if flat is None else flat)[off:off + int(np.prod(shape))]
+        if name in self.ints:
+            v = v.view(torch.int32) if isinstance(v, torch.Tensor) else v.view(np.int32)
+        return v.reshape(shape)
+
+
+def memory_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, batch: int = EVAL_BATCH,
+                    indices: bool = False) -> Dict[str, np.ndarray]:
+    """Which clips the memory does not hold: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and on the model's
+    device -> per-frame numpy arrays of the sub-video.  `rgb_comm` / `op_comm` [T]: the reference's value, ONE number per
+    batch written to every frame of it (unchanged).  `rgb_clip_comm` / `op_clip_comm` [T]: the commit distance of the
+    frame's own clip, a function of that clip's bottleneck alone; `*_commit_map` [T,H/8,W/8]: the same per position of
+    the bottleneck grid; `*_commit_worst`, `*_commit_worst_idx`: its largest value and where; `*_psnr`; with `indices`
+    `*_slots` [T,H/8,W/8,k] int32, the memory items each position addresses.  Clips, targets, batches, frame indexing and
+    fills are `localise_subvideo`'s; behind every forward `ops.memory_scores` runs on each stream's bottleneck
+    (`model.bottleneck_inputs()`) with that stream's `vq_down3`.  One device-to-host copy per sub-video; a batch whose
+    S16 range flag is set is re-run with `exact=True`, and its memory pass with it."""
+    from . import ops
+    t = rgb_frames.shape[0]
+    if op_frames.shape[0] != t - 1:
+        raise ValueError("a sub-video of T frames has T-1 flows")
+    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
+        raise ValueError("memory_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
+    batches = subvideo_batches(t, batch)
+    if not batches:
+        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
+    n_clip = batches[-1][1]
+    quans = {"rgb": model.rgb.vq_down3, "op": model.op.vq_down3}
+    ks = {st: int(getattr(q, "quan", q).quantize.k) for st, q in quans.items()}
+    sections, ints = [], []
+    for st, frames in (("rgb", rgb_frames), ("op", op_frames)):
+        h, w = frames.shape[2] // 8, frames.shape[3] // 8
+        sections += [(f"{st}_commit_map", (n_clip, h, w)), (f"{st}_clip_comm", (n_clip,)), (f"{st}_commit_worst", (n_clip,)),
+                     (f"{st}_commit_worst_idx", (n_clip,)), (f"{st}_psnr", (n_clip,))]
+        ints.append(f"{st}_commit_worst_idx")
+        if indices:
+            sections.append((f"{st}_slots", (n_clip, h, w, ks[st])))
+            ints.append(f"{st}_slots")
+    sections += [("comm", (len(batches), 2)), ("flag", (len(batches),))]
+    slots = _FlatSlots(sections, ints, rgb_frames.device)
+
+    def run(k: int, exact: bool):
+        s, e = batches[k]
+        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
+        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
+        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        with torch.no_grad():
+            (_, _, diffs, _), *psnr = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
+            flag = getattr(model, "last_overflow", None)
+            for st, x4, ps in zip(("rgb", "op"), model.bottleneck_inputs(), psnr):
+                out = {"map": slots.view(f"{st}_commit_map")[s:e], "commit": slots.view(f"{st}_clip_comm")[s:e],
+                       "worst": slots.view(f"{st}_commit_worst")[s:e], "worst_idx": slots.view(f"{st}_commit_worst_idx")[s:e]}
+                if indices:
+                    out["idx"] = slots.view(f"{st}_slots")[s:e]
+                ops.memory_scores(quans[st], x4.permute(0, 3, 1, 2), indices, out)
+                slots.view(f"{st}_psnr")[s:e] = ps
+            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
+            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
+
+    for k in range(len(batches)):
+        run(k, False)
+    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
+    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
+    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
+        for k in flagged:
+            run(k, True)
+            _count_fallback(model)
+        host = slots.flat.cpu().numpy()
+    names = [n for n, _ in sections if n not in ("comm", "flag")]
+    parts = []
+    for k, (s, e) in enumerate(batches):
+        part = {n: slots.view(n, host)[s:e] for n in names}
+        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
+        parts.append(part)
+    return assemble_localised(t, batches, parts)
+
+
+def evaluate_dataset_memory(model, videos, dataset_name: str = "synthetic", indices: bool = False,
+                            maps_dir: Optional[str] = None, device=None, batch: int = EVAL_BATCH) -> dict:
+    """`evaluate_dataset` with `memory_subvideo` in place of the scoring loop (one rank).  `videos`: a sequence of
+    (rgb_frames, op_frames) - host tensors are moved to `device` (default: the model's) one sub-video at a time - or an
+    iterator of device-resident sub-videos (`pipeline.SubVideoStager`).  Returns the four record lists of the reference
+    (`*_fea_comm_records`: one value per batch, as the reference writes them) plus `rgb_clip_comm_records` /
+    `op_clip_comm_records` (the per-clip commit distance per frame: drop-ins for the `*_fea_comm_records` in
+    `fuse_scores_auc`), `n_frames` and `map_files`.  `maps_dir`: one `NNNN.npz` per sub-video with the arrays of
+    `memory_subvideo`."""
+    if device is None:
+        device = next(model.parameters()).device
+    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
+           "op_fea_comm_records": [], "rgb_clip_comm_records": [], "op_clip_comm_records": [], "n_frames": [], "map_files": []}
+    if maps_dir:
+        os.makedirs(maps_dir, exist_ok=True)
+    for v, (rgb, op) in enumerate(videos):
+        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+        rec = memory_subvideo(model, rgb, op, batch, indices)
+        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
+        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
+        out["op_img_pred_records"].append(rec["op_psnr"])
+        out["op_fea_comm_records"].append(rec["op_comm"])
+        out["rgb_clip_comm_records"].append(rec["rgb_clip_comm"])
+        out["op_clip_comm_records"].append(rec["op_clip_comm"])
+        out["n_frames"].append(int(rgb.shape[0]))
+        if maps_dir:
+            path = os.path.join(maps_dir, f"{v:04d}.npz")
+            np.savez(path, **rec)
+            out["map_files"].append(path)
+    return out
+
+
 # AMMC_FUSED_LOSS: 1 = the per-pixel terms of the generator's objective (intensity, gradient difference, flow) come from the
 # library's loss kernels (`losses.py`: one forward and one backward launch per prediction pair), 0 (default) = the torch
 # chains below.  Device tensors only: on the CPU the flag changes nothing.  profiles/loss_ab.txt holds the A/B.

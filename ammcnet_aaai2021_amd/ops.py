@@ -220,6 +220,82 @@ def error_maps(pred: torch.Tensor, target: torch.Tensor, patch: int = 16, pixel:
     return res
 
 
+def _nhwc_strides(t: torch.Tensor):
+    """(batch, row, pixel) strides of an NHWC view [B, h, w, C] for `ammc_memory_scores_f32`; a dimension of size 1 may
+    carry any stride in torch - it is given the extent below it instead"""
+    b, h, w, c = t.shape
+    bs, rs, ps, _ = t.stride()
+    if w == 1:
+        ps = max(ps, c)
+    row = (w - 1) * ps + c
+    if h == 1:
+        rs = max(rs, row)
+    if b == 1:
+        bs = max(bs, (h - 1) * rs + row)
+    return bs, rs, ps
+
+
+def memory_scores(quan, x: torch.Tensor, indices: bool = False, out: dict | None = None) -> dict:
+    """Per-clip memory-commit scores (csrc/memory_scores.hip; definitions in include/ammc_hip.h).  `quan`: an
+    `enc_quan_dec_topk` / `enc_quan_dec_res_topk` module - its `enc.weight`, `enc.bias`, `quantize.embed` and
+    `quantize.k` are read.  `x`: the bottleneck in front of it, fp32 [B, C, h, w] NCHW-SHAPED on the GPU with any strides;
+    the kernel reads its NHWC view in place when that view's channel stride is 1 (a permuted NHWC tensor, a workspace
+    view); otherwise - a plain contiguous NCHW tensor - ONE channels-last copy is made first.  Returns `map` [B, h, w]
+    (the squared distance to the nearest slot / d per position), `commit` [B] (its fixed-order mean), `worst` [B],
+    `worst_idx` [B] int32 (the largest map value and the lowest y * w + x attaining it) and, with `indices`, `idx`
+    [B, h, w, k] int32 (the k nearest slots, nearest first).  A clip's outputs do not depend on the batch it is in.  Two
+    launches on torch's current stream behind the codebook pack.  `out`: tensors to write into, by the same keys (views of
+    per-sub-video buffers) - `map` with contiguous clips and any batch stride, the others contiguous."""
+    _need_cuda(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("memory_scores: x must be an fp32 [B, C, h, w] tensor")
+    quan = getattr(quan, "quan", quan)                        # enc_quan_dec_res_topk wraps the block it adds `x` to
+    q = quan.quantize
+    enc_w, enc_b, embed = quan.enc.weight.detach(), quan.enc.bias.detach(), q.embed.detach()
+    d, m, k = int(embed.shape[0]), int(embed.shape[1]), int(q.k)
+    B, c, h, w = x.shape
+    if tuple(enc_w.shape) != (d, c, 1, 1):
+        raise ValueError(f"memory_scores: enc.weight {tuple(enc_w.shape)} does not map {c} channels to the codebook's {d}")
+    dev = x.device
+    if enc_w.device != dev or embed.device != dev:
+        raise ValueError("memory_scores: the module and x must be on one device")
+    lib = _lib.load()
+    xv = x.detach().permute(0, 2, 3, 1)
+    if xv.stride(3) != 1:
+        xv = xv.contiguous()                                  # the one copy: NCHW-contiguous input -> channels last
+    enc_w, enc_b, embed = enc_w.float().contiguous(), enc_b.float().contiguous(), embed.float().contiguous()
+    e_md, enorm = _Packer(dev).codebook(embed)
+    out = dict(out) if out else {}
+    want = {"map": ((B, h, w), torch.float32), "commit": ((B,), torch.float32), "worst": ((B,), torch.float32),
+            "worst_idx": ((B,), torch.int32)}
+    if indices:
+        want["idx"] = ((B, h, w, k), torch.int32)
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"memory_scores: `out` has no slot {sorted(unknown)}")
+    res = {}
+    for key, (shape, dtype) in want.items():
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise ValueError(f"memory_scores: out[{key!r}] must be {dtype} {shape} on {dev}")
+        elif key == "map":
+            if not t[0].is_contiguous() or (B > 1 and t.stride(0) < h * w):
+                raise ValueError("memory_scores: out['map']: the map of a clip must be contiguous (any batch stride)")
+        elif not t.is_contiguous():
+            raise ValueError(f"memory_scores: out[{key!r}] must be contiguous")
+        res[key] = t
+    mp = res["map"]
+    map_bs = max(mp.stride(0), h * w) if B == 1 else mp.stride(0)
+    idx = res.get("idx")
+    _lib.check(lib.ammc_memory_scores_f32(_ptr(xv), *_nhwc_strides(xv), B, h, w, c, _ptr(enc_w), _ptr(enc_b), _ptr(embed),
+                                          _ptr(e_md), _ptr(enorm), d, m, k, _ptr(mp), map_bs,
+                                          idx.data_ptr() if idx is not None else None, _ptr(res["commit"]), _ptr(res["worst"]),
+                                          res["worst_idx"].data_ptr(), _stream(x)), "memory_scores")
+    return res
+
+
 def embed_rows(embed: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     """`Quantize_topk.embed_code` (unet.py:315-316): rows of the transposed codebook"""
     return embed.t()[ids]

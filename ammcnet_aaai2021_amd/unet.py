@@ -314,6 +314,16 @@ class twostream(nn.Module):
         eng, _, a = self._quant_src
         return eng.act_nchw(a) if eng is not None else a.interior().permute(0, 3, 1, 2)
 
+    def bottleneck_inputs(self):
+        """the last EVALUATION forward's bottleneck in front of the memory block of both streams, (rgb, op), as fp32 NHWC
+        tensors [B, h/8, w/8, 512] (`EvalEngine.bottleneck_inputs`: views for fp32 plans, exactly decoded copies for S16
+        plans; after an `exact=True` re-run or a range fallback the fp32 engine's).  `quant_befor` serves the rgb stream
+        only.  Valid until the next forward of that shape."""
+        eng = getattr(self, "_quant_src", (None,))[0]
+        if eng is None:
+            raise RuntimeError("bottleneck_inputs serves evaluation forwards: call .eval() and run a forward first")
+        return eng.bottleneck_inputs()
+
 
 def get_unet(in_channel, out_channel, embed_dim=0, n_embed=0, k=0):
     return UNet(in_channel, out_channel)

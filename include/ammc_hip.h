@@ -715,6 +715,40 @@ int ammc_error_maps_f32(const float* pred, int64_t p_bs, int64_t p_cs, int64_t p
                         float* patch_sum, int64_t ps_bs, float* patch_mean, float* pixel, int64_t px_bs, float* frame_sq,
                         float* worst, int32_t* worst_idx, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-clip memory-commit scores (csrc/memory_scores.hip): the memory module's commitment distance per position and per
+ * clip, from a pass of its own over the bottleneck in front of the memory block.  x: fp32 NHWC [batch][h][w][c],
+ * channel stride 1, batch / row / pixel strides in floats.  enc_w [d][c] and enc_b [d]: the module's `enc` 1x1 as it
+ * lies in memory (no packing).  embed_dm [d][m]: the module buffer E; embed_md [m][d], enorm [m] from
+ * ammc_pack_codebook_f32.  With p a position of clip b:
+ *   z[p][j]       = (sum_i x[p][i] * enc_w[j][i]) + enc_b[j] in fp32.  The channels are added in chains of at most 64
+ *                   consecutive ones (fmaf chains from 0, in channel order), the chains are added in order, the bias
+ *                   last: the order is a function of c alone
+ *   r[p][s]       = enorm[s] - 2 * sum_j z[p][j] * E[j][s] in fp32 (one fmaf chain over j = 0, 1, ... from 0): the
+ *                   reference's `dist` (models/unet.py:284-288) without its row-constant |z|^2
+ *   idx[p][0..k)  = the k smallest keys, nearest first; exactly equal keys in ascending slot order
+ *   s[p]          = sum_j (E[j][idx0] - z[p][j])^2, j = 0, 1, ... in order, each square a rounded product: taken
+ *                   directly from the fp32 data, never from the expanded form
+ *   map[b][y][x]  = s[p] / d                    (rows w floats apart, clips map_bs floats apart)
+ *   idx_topk      int32 [batch][h][w][k], dense; may be NULL
+ *   commit[b]     = (float)(S / (h * w)): for each row y a double adds (double)map[b][y][0], [y][1], ... in that order,
+ *                   a second double adds the rows in order, that total is S (the construction of frame_sq above)
+ *   worst[b]      the largest stored map[b] value, bit for bit;  worst_idx[b] the lowest y * w + x that attains it
+ * Two launches, no atomics, no arrival counter, no allocation: every output has one writer.  The outputs of clip b are
+ * a function of (x[b], enc_w, enc_b, E, h, w, c, m, k) and of nothing else - not the batch size, the clip's place in
+ * the batch, a stride or an alignment (16-byte loads where the bases and strides allow, 4-byte loads otherwise), nor
+ * whether idx_topk was asked for.  A NaN or +inf key never ranks; where fewer than k keys of a position rank the empty
+ * places report slot m - 1.  worst / worst_idx are UNSPECIFIED for a clip whose map holds a NaN.
+ * AMMC_EINVAL: a null pointer other than idx_topk; pointers not 4-byte aligned; batch, h, w, c, d, m or k <= 0;
+ * x_ps < c; a row / batch stride smaller than the extent below it; map_bs < h * w.
+ * AMMC_EUNSUP: d != 64; k > 2; c % 32 != 0 or c > 1024; m < k; h * w > 2^31 - 64 or batch * ceil(h w / 64) >= 2^31.
+ * All of them are decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_memory_scores_f32(const float* x, int64_t x_bs, int64_t x_rs, int64_t x_ps, int32_t batch, int32_t h, int32_t w,
+                           int32_t c, const float* enc_w, const float* enc_b, const float* embed_dm, const float* embed_md,
+                           const float* enorm, int32_t d, int32_t m, int32_t k, float* map, int64_t map_bs, int32_t* idx_topk,
+                           float* commit, float* worst, int32_t* worst_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
