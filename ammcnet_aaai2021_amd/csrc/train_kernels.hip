@@ -400,6 +400,28 @@ __global__ __launch_bounds__(256) void scale_shift_act_s16_kernel(
   *reinterpret_cast<ss_f16x8*>(y16 + oo + 4) = lo;
 }
 
+// One element of the BatchNorm-backward apply pass, dc = scale (g - sum_g / M - xhat sum_gx / M) with g = dy [pre > 0],
+// its roundings spelled out: xhat = fl(fl(c - mean) invstd), pre = fma(c, scale, shift) (the forward's expression),
+// then  fl(scale * fma(-1/M, fl(xhat sum_gx), fl(g - sg_ic)))  with sg_ic = fl(sum_g / M), a per-channel constant.  That
+// is what the compiler makes of the plain expression in the row forms (bn_bwd_apply_s16_rows_kernel, the timed path: it
+// hoists sum_g / M out of their loops, so that product cannot fuse into the subtraction).  In the one-item forms the same
+// expression was contracted the other way - fma(-1/M, sum_g, g) - and they differed from the row forms by an ulp
+// (tests/test_gpu_s16_stream_kernels.py).  bn_bwd_apply_kernel and bn_bwd_apply_s16_kernel now call
+// this function; the row forms' code and bits are unchanged, and the tests hold the three to the same bits.
+__device__ __forceinline__ float bn_bwd_dc(float c, float dy, float mu, float is, float ga, float be, float sg_ic, float sgx,
+                                           float inv_count, int relu) {
+#pragma clang fp contract(off)                          // (__fmul_rn / __fsub_rn are plain operators here: they would still fuse)
+  const float xh = (c - mu) * is;
+  const float pre = __builtin_fmaf(c, ga, be);          // ga = folded scale (gamma * invstd), be = folded shift
+  const float gi = (!relu || pre > 0.f) ? dy : 0.f;
+  return ga * __builtin_fmaf(-inv_count, xh * sgx, gi - sg_ic);
+}
+
+__device__ __forceinline__ float bn_bwd_sg_ic(float sg, float inv_count) {
+#pragma clang fp contract(off)
+  return sg * inv_count;
+}
+
 // dc = gamma * invstd * (g - sum_g / M - xhat * sum_gx / M),  g = dy * [pre > 0]
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float* __restrict__ c, Tensor3 ct, const float* __restrict__ dy, Tensor3 dt,
@@ -425,12 +447,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   const f32x4 sgx = *reinterpret_cast<const f32x4*>(sums + C + c4 * 4);
   f32x4 o;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float xh = (v[i] - mu[i]) * is[i];
-    const float pre = v[i] * ga[i] + be[i];             // ga = folded scale (gamma*invstd), be = folded shift
-    const float gi = (!relu || pre > 0.f) ? g[i] : 0.f;
-    o[i] = ga[i] * (gi - sg[i] * inv_count - xh * sgx[i] * inv_count);
-  }
+  for (int i = 0; i < 4; ++i)
+    o[i] = bn_bwd_dc(v[i], g[i], mu[i], is[i], ga[i], be[i], bn_bwd_sg_ic(sg[i], inv_count), sgx[i], inv_count, relu);
   if (live) *reinterpret_cast<f32x4*>(dc + pix_off(m, H, W, ot) + c4 * 4) = o;
   if (amax_bits) {       // largest |dc| of the tensor, for the S16 re-encoding of this gradient (ammc_absmax_bits_f32)
     __shared__ float wmax[4];
@@ -573,12 +591,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s16_kernel(
     const f32x4 sg = *reinterpret_cast<const f32x4*>(sums + cc);
     const f32x4 sgx = *reinterpret_cast<const f32x4*>(sums + C + cc);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float xh = (v[i] - mu[i]) * is[i];
-      const float pre = v[i] * ga[i] + be[i];
-      const float gi = (!relu || pre > 0.f) ? g[i] : 0.f;
-      o[half * 4 + i] = ga[i] * (gi - sg[i] * inv_count - xh * sgx[i] * inv_count);
-    }
+    for (int i = 0; i < 4; ++i)
+      o[half * 4 + i] = bn_bwd_dc(v[i], g[i], mu[i], is[i], ga[i], be[i], bn_bwd_sg_ic(sg[i], inv_count), sgx[i], inv_count, relu);
   }
   const int64_t oo = pix_off(m, H, W, ot) + c8 * 8;
   if (dc32) {
@@ -1154,7 +1168,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s16_rows_kernel(
           const float xh = (v[u][h][i] - mu[h][i]) * is[h][i];
           const float pre = v[u][h][i] * ga[h][i] + be[h][i];
           const float gi = (!relu || pre > 0.f) ? g[u][h][i] : 0.f;
-          o[h * 4 + i] = ga[h][i] * (gi - sg[h][i] * inv_count - xh * sgx[h][i] * inv_count);
+          o[h * 4 + i] = ga[h][i] * (gi - sg[h][i] * inv_count - xh * sgx[h][i] * inv_count);      // = bn_bwd_dc, see there
         }
       const int64_t op = orow + oo + u * od;
       if (dc32) {

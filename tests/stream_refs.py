@@ -118,7 +118,26 @@ def maxpool2x2_bwd(x, dp, add=None):
     return dx + d(add) if add is not None else dx
 
 
+def unpool2x2(dp, arg, fh, fw):
+    """MaxPool2d(2) backward from recorded window positions: dp [B, h, w, C] routed to position arg (0..3, row-major) of its
+    window in an fh x fw tensor; a last odd row / column is in no window and stays zero"""
+    dp, arg = d(dp), torch.as_tensor(arg).to("cpu", torch.int64)
+    b, h, w, c = dp.shape
+    dx = torch.zeros(b, fh, fw, c, dtype=F64)
+    for j in range(4):
+        dx[:, (j >> 1):2 * h:2, (j & 1):2 * w:2] = torch.where(arg == j, dp, torch.zeros_like(dp))
+    return dx
+
+
 # ---- activations -----------------------------------------------------------------------------------------------------
+
+def scale_shift_act(x, scale, shift, res=None, relu=0):
+    """y = act(x scale + shift) + res (the apply pass of a BatchNorm unit on its folded scale / shift)"""
+    y = d(x) * d(scale) + d(shift)
+    if relu:
+        y = y.clamp_min(0.0)
+    return y + d(res) if res is not None else y
+
 
 def tanh_bwd_nhwc(dout_nchw, out_nchw, cp):
     """dout (1 - out^2), NCHW -> NHWC with channels [C, cp) zero"""

@@ -1,4 +1,9 @@
-"""The C-ABI entry points added in round 4, each against an fp64 / composition reference through ctypes:
+"""The C-ABI entry points added in round 4 through ctypes.  The convolution and weight-gradient cases are compared with
+float64 `conv2d` / autograd; the rest are COMPOSITION checks, not references: `ammc_pack_filters_s16` against pack + split,
+`test_bn_apply_with_pooled_output_equals_apply_then_pool` and `test_bn_backward_with_the_max_pool_gradient_formed_on_the_fly`
+against the unfused passes, bit for bit - both sides share the tie rule, the mask and the encoder, so an error made twice
+passes here.  The independent fp64 / codec references of these kernels are tests/test_gpu_s16_stream_kernels.py.
+Covered here:
   * `ammc_conv_wgrad_s16` with 4x4 windows at stride 1 | 2 (PixelDiscriminator) and the 2x2 stride-2 window of a
     ConvTranspose's weight gradient (the generalised im2col form of csrc/wgrad_s16.hip);
   * `ammc_conv_gemm_s16` with a 4x4 window, stride 2 and the LeakyReLU epilogue, S16 and fp32 outputs;
