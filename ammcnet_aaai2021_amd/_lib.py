@@ -178,6 +178,9 @@ SIGNATURES = {
     "ammc_error_maps_patch_count": (C.c_int, [_i32, _i32, _i32]),
     "ammc_error_maps_f32": (C.c_int, [_p] + _s3 + [_p] + _s3 + [_i32] * 5 + [_p, _i64, _p, _p, _i64, _p, _p, _p, _p]),
     "ammc_memory_scores_f32": (C.c_int, [_p] + _s3 + [_i32] * 4 + [_p] * 5 + [_i32] * 3 + [_p, _i64, _p, _p, _p, _p, _p]),
+    "ammc_ssim_tile": (C.c_int, []),
+    "ammc_ssim_workspace_floats": (C.c_int64, [_i32] * 4),
+    "ammc_ssim_f32": (C.c_int, [_p] + _s3 + [_p] + _s3 + [_i32] * 4 + [_p, _p, _p, _p, _p, _i64, _p, _i64, _p]),
 }
 
 _lib = None

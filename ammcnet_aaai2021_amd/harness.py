@@ -577,6 +577,139 @@ def evaluate_dataset_memory(model, videos, dataset_name: str = "synthetic", indi
     return out
 
 
+# ---- SSIM and MSE frame scores --------------------------------------------------------------
+# A pass of its own behind the evaluation forward (`ops.ssim`, csrc/ssim.hip): the two record types of the reference's
+# evaluation loop beside PSNR (`loss_name` = ssim_error / mse_error, run_helper/test_helper.py:28-33, 396-400).  The
+# scoring loops above and the fused epilogue sums they read are not touched.
+
+def ssim_reference(pred: torch.Tensor, target: torch.Tensor, dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    """the quantities of `ops.ssim` with plain torch in `dtype` (any device; float64: the reference of the tests;
+    float32: the reference's own arithmetic, utils/pytorch_ssim.py:20-40).  The window is the 2-D one exactly as the
+    reference forms it - the fp32 outer product of the fp32 1-D window - then cast; zero padding; C1 = 0.01^2,
+    C2 = 0.03^2 on the values as they are.  `map_c` [B,C,H,W] the SSIM map, `map` [B,H,W] its channel mean, `ssim_c`
+    [B,C], `ssim` [B] (the reference's `size_average=False` value per sample), `sq` [B] = the sum of (target - pred)^2,
+    `mse` = 256 sq / (C H W) (utils/utils.py:110-111), `psnr` = 10 log10(4 C H W / sq)."""
+    import torch.nn.functional as F
+    from .ops import ssim_window
+    b, c, h, w = pred.shape
+    w1 = ssim_window().unsqueeze(1)
+    window = w1.mm(w1.t()).float().to(device=pred.device, dtype=dtype).expand(c, 1, 11, 11).contiguous()
+    x1, x2 = pred.to(dtype), target.to(dtype)
+
+    def conv(t):
+        return F.conv2d(t, window, padding=5, groups=c)
+    mu1, mu2 = conv(x1), conv(x2)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1.pow(2), mu2.pow(2), mu1 * mu2
+    sigma1_sq = conv(x1 * x1) - mu1_sq
+    sigma2_sq = conv(x2 * x2) - mu2_sq
+    sigma12 = conv(x1 * x2) - mu1_mu2
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    map_c = ((2 * mu1_mu2 + c1) * (2 * sigma12 + c2)) / ((mu1_sq + mu2_sq + c1) * (sigma1_sq + sigma2_sq + c2))
+    sq = ((x2 - x1) ** 2).sum(dim=(1, 2, 3))
+    n = float(c * h * w)
+    return {"map_c": map_c, "map": map_c.mean(1), "ssim_c": map_c.mean(dim=(2, 3)), "ssim": map_c.mean(1).mean(1).mean(1),
+            "sq": sq, "mse": 256.0 * sq / n, "psnr": 10.0 * torch.log10(4.0 * n / sq)}
+
+
+def quality_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, maps: bool = False, batch: int = EVAL_BATCH,
+                     predictions: Optional[list] = None) -> Dict[str, np.ndarray]:
+    """The reference's three frame scores of one sub-video: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and
+    on the model's device -> per-frame numpy arrays `rgb_ssim` / `op_ssim`, `rgb_mse` / `op_mse`, `rgb_psnr` / `op_psnr`
+    (all three from `ops.ssim`: fixed-order sums, the same bits for the same predictions), `rgb_comm` / `op_comm` [T], and
+    with `maps` `rgb_ssim_map` / `op_ssim_map` [T,H,W].  Clips, targets and batches are those of `localise_subvideo`
+    (`batch` clips at a time), the forward is the model's evaluation forward, frame indexing and fills are
+    `assemble_records`' (`assemble_localised`).  Every batch is queued back to back; one flat device buffer and one
+    device-to-host copy per sub-video; a batch whose S16 range flag is set is re-run with `exact=True`.  `predictions`:
+    the testing hook of `localise_subvideo` - a list that receives (s, e, rgb_pred, op_pred, fused) of every batch."""
+    from . import ops
+    t = rgb_frames.shape[0]
+    if op_frames.shape[0] != t - 1:
+        raise ValueError("a sub-video of T frames has T-1 flows")
+    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
+        raise ValueError("quality_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
+    batches = subvideo_batches(t, batch)
+    if not batches:
+        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
+    n_clip = batches[-1][1]
+    sections = []
+    for st, frames in (("rgb", rgb_frames), ("op", op_frames)):
+        sections += [(f"{st}_{k}", (n_clip,)) for k in ("ssim", "mse", "psnr")]
+        if maps:
+            sections.append((f"{st}_ssim_map", (n_clip,) + tuple(frames.shape[2:])))
+    sections += [("comm", (len(batches), 2)), ("flag", (len(batches),))]
+    slots = _FlatSlots(sections, (), rgb_frames.device)
+
+    def run(k: int, exact: bool):
+        s, e = batches[k]
+        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
+        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
+        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        with torch.no_grad():
+            (rgb_out, op_out, diffs, _), *fused = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
+            flag = getattr(model, "last_overflow", None)
+            for st, pred, tgt in (("rgb", rgb_out, targets[0]), ("op", op_out, targets[1])):
+                out = {"ssim": slots.view(f"{st}_ssim")[s:e]}
+                if maps:
+                    out["map"] = slots.view(f"{st}_ssim_map")[s:e]
+                got = ops.ssim(pred, tgt, maps, out)
+                slots.view(f"{st}_mse")[s:e] = got["mse"]
+                slots.view(f"{st}_psnr")[s:e] = got["psnr"]
+            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
+            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
+        return (s, e, rgb_out, op_out, fused) if predictions is not None else None      # (else the frames are let go)
+
+    done = [run(k, False) for k in range(len(batches))]
+    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
+    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
+    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
+        for k in flagged:
+            done[k] = run(k, True)
+            _count_fallback(model)
+        host = slots.flat.cpu().numpy()
+    if predictions is not None:
+        predictions.extend(done)
+    names = [n for n, _ in sections if n not in ("comm", "flag")]
+    parts = []
+    for k, (s, e) in enumerate(batches):
+        part = {n: slots.view(n, host)[s:e] for n in names}
+        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
+        parts.append(part)
+    return assemble_localised(t, batches, parts)
+
+
+def evaluate_dataset_quality(model, videos, dataset_name: str = "synthetic", maps: bool = False,
+                             maps_dir: Optional[str] = None, device=None) -> dict:
+    """`evaluate_dataset` with `quality_subvideo` in place of the scoring loop (one rank).  `videos`: a sequence of
+    (rgb_frames, op_frames) - host tensors are moved to `device` (default: the model's) one sub-video at a time - or an
+    iterator of device-resident sub-videos (`pipeline.SubVideoStager`).  Returns the four record lists of the reference
+    with `*_img_pred_records` from the fixed-order squared error (the reference's records for `loss_name` = psnr_error),
+    plus `rgb_ssim_records` / `op_ssim_records` (ssim_error) and `rgb_mse_records` / `op_mse_records` (mse_error),
+    `n_frames` and `map_files`.  `maps_dir`: one `NNNN.npz` per sub-video with the arrays of `quality_subvideo`."""
+    if device is None:
+        device = next(model.parameters()).device
+    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
+           "op_fea_comm_records": [], "rgb_ssim_records": [], "op_ssim_records": [], "rgb_mse_records": [],
+           "op_mse_records": [], "n_frames": [], "map_files": []}
+    if maps_dir:
+        os.makedirs(maps_dir, exist_ok=True)
+    for v, (rgb, op) in enumerate(videos):
+        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+        rec = quality_subvideo(model, rgb, op, maps)
+        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
+        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
+        out["op_img_pred_records"].append(rec["op_psnr"])
+        out["op_fea_comm_records"].append(rec["op_comm"])
+        for st in ("rgb", "op"):
+            out[f"{st}_ssim_records"].append(rec[f"{st}_ssim"])
+            out[f"{st}_mse_records"].append(rec[f"{st}_mse"])
+        out["n_frames"].append(int(rgb.shape[0]))
+        if maps_dir:
+            path = os.path.join(maps_dir, f"{v:04d}.npz")
+            np.savez(path, **rec)
+            out["map_files"].append(path)
+    return out
+
+
 # AMMC_FUSED_LOSS: 1 = the per-pixel terms of the generator's objective (intensity, gradient difference, flow) come from the
 # library's loss kernels (`losses.py`: one forward and one backward launch per prediction pair), 0 (default) = the torch
 # chains below.  Device tensors only: on the CPU the flag changes nothing.  profiles/loss_ab.txt holds the A/B.

@@ -220,6 +220,87 @@ def error_maps(pred: torch.Tensor, target: torch.Tensor, patch: int = 16, pixel:
     return res
 
 
+SSIM_TILE = 32               # tile edge of csrc/ssim.hip (`ammc_ssim_tile()`): where a frame is cut for its fixed-order sums
+SSIM_MAX_CHANNELS = 4
+_ssim_window_c = None
+_ssim_workspaces: dict = {}
+
+
+def ssim_window() -> torch.Tensor:
+    """the reference's 1-D window (utils/pytorch_ssim.py:8-10): exp(-(x - 5)^2 / (2 * 1.5^2)) taken in double, rounded to
+    fp32, divided by the fp32 sum; [11] fp32 on the CPU"""
+    import math
+    g = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)], dtype=torch.float32)
+    return g / g.sum()
+
+
+def _ssim_workspace(dev: torch.device, stream: int, floats: int) -> torch.Tensor:
+    """the tile partials of `ssim`, cached per (device, stream): launches on one stream run in order, so the next call's
+    first launch cannot overtake this call's second one; it only grows"""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
+    ws = _ssim_workspaces.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _ssim_workspaces[key] = torch.empty(max(floats, 4096), device=dev, dtype=torch.float32)
+    return ws
+
+
+def ssim(pred: torch.Tensor, target: torch.Tensor, map: bool = False, out: dict | None = None) -> dict:
+    """The reference's SSIM and MSE frame scores (csrc/ssim.hip; definitions in include/ammc_hip.h): `pred`, `target` fp32
+    [B, C, H, W] on the GPU, C <= 4, pixel stride 1, any batch / channel / row strides (nothing is copied), values as they
+    are (the reference scores its [-1, 1] frames).  Returns `ssim` [B] (the reference's `ssim_error` of each sample),
+    `ssim_c` [B, C], `sq` [B] (the sum of (target - pred)^2), `map` [B, H, W] when asked (the channel mean of the SSIM
+    map), and derived from `sq`: `mse` = 256 sq / (C H W) (the reference's `mse_error`) and `psnr` = 10 log10(4 C H W / sq).
+    Two launches on torch's current stream; every sum is taken in a fixed order, so equal inputs give equal bits wherever
+    the sample stands in a batch.  `out`: tensors to write into, by the keys `ssim`, `ssim_c`, `sq`, `map` (views of
+    per-sub-video buffers) - the map of a sample contiguous with any batch stride, the others contiguous."""
+    global _ssim_window_c
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"ssim: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be equal [B, C, H, W] shapes")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32 or pred.device != target.device:
+        raise ValueError("ssim: fp32 tensors on one device")
+    if pred.stride(3) != 1 or target.stride(3) != 1:
+        raise ValueError("ssim: pixel stride 1 (NCHW views; make channels-last tensors contiguous first)")
+    B, C, H, W = pred.shape
+    dev = pred.device
+    out = dict(out) if out else {}
+    want = {"ssim": (B,), "ssim_c": (B, C), "sq": (B,)}
+    if map:
+        want["map"] = (B, H, W)
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"ssim: `out` has no slot {sorted(unknown)}")
+    _need_cuda(pred)
+    lib = _lib.load()
+    res = {}
+    for key, shape in want.items():
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=torch.float32)
+        elif tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"ssim: out[{key!r}] must be torch.float32 {shape} on {dev}")
+        elif key == "map":
+            if not t[0].is_contiguous() or (B > 1 and t.stride(0) < H * W):
+                raise ValueError("ssim: out['map']: the map of a sample must be contiguous (any batch stride)")
+        elif not t.is_contiguous():
+            raise ValueError(f"ssim: out[{key!r}] must be contiguous")
+        res[key] = t
+    if _ssim_window_c is None:
+        import ctypes
+        _ssim_window_c = (ctypes.c_float * 11)(*ssim_window().tolist())
+    mp = res.get("map")
+    map_bs = 0 if mp is None else (max(mp.stride(0), H * W) if B == 1 else mp.stride(0))
+    stream = _stream(pred)
+    floats = int(lib.ammc_ssim_workspace_floats(B, C, H, W))
+    ws = _ssim_workspace(dev, stream, floats)
+    _lib.check(lib.ammc_ssim_f32(_ptr(pred), *_nchw_strides(pred), _ptr(target), *_nchw_strides(target), B, C, H, W,
+                                 _ssim_window_c, _ptr(res["ssim"]), _ptr(res["ssim_c"]), _ptr(res["sq"]),
+                                 _ptr(mp) if mp is not None else None, map_bs, _ptr(ws), ws.numel(), stream), "ssim")
+    n = float(C * H * W)
+    res["mse"] = 256.0 * res["sq"] / n
+    res["psnr"] = 10.0 * torch.log10(4.0 * n / res["sq"])
+    return res
+
+
 def _nhwc_strides(t: torch.Tensor):
     """(batch, row, pixel) strides of an NHWC view [B, h, w, C] for `ammc_memory_scores_f32`; a dimension of size 1 may
     carry any stride in torch - it is given the extent below it instead"""

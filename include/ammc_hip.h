@@ -749,6 +749,57 @@ int ammc_memory_scores_f32(const float* x, int64_t x_bs, int64_t x_rs, int64_t x
                            const float* enorm, int32_t d, int32_t m, int32_t k, float* map, int64_t map_bs, int32_t* idx_topk,
                            float* commit, float* worst, int32_t* worst_idx, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SSIM and squared-error frame scores (csrc/ssim.hip): the reference's `ssim_error` (utils/pytorch_ssim.py) and the sum
+ * its `mse_error` / `psnr_error` are functions of, from a pass of its own over a predicted frame and its target.
+ * pred / target: fp32 [batch][c][h][w] views, pixel stride 1, batch / channel / row strides in floats (the targets of a
+ * batch are a slice of a resident sub-video).  The values are used AS THEY ARE: the reference applies C1 = 0.01^2 and
+ * C2 = 0.03^2 (rounded to fp32) to its frames on [-1, 1] without rescaling them to [0, 1], and so does this pass.
+ * win: a HOST array of 11 floats, read during the call: the reference's 1-D window, exp(-(x - 5)^2 / (2 * 1.5^2)) taken
+ * in double, rounded to fp32 and divided by the fp32 sum.  With f = 0 outside the frame (a tap there adds an exact + 0):
+ *   G(f)(y, x)      = sum_i win[i] * (sum_j win[j] * f(y + i - 5, x + j - 5)): the row pass over j = 0..10, then the
+ *                     column pass over i = 0..10, each ONE fmaf chain from 0 in tap order.  (The reference convolves
+ *                     with the fp32-rounded outer product of win; on the map the two differ by 1e-7 .. 3e-7 in exact
+ *                     arithmetic, below the fp32 noise of either.  The separable form is the definition here.)
+ *   mu1 = G(pred), mu2 = G(target), s1 = G(pred * pred) - mu1 * mu1, s2 = G(target * target) - mu2 * mu2,
+ *   s12 = G(pred * target) - mu1 * mu2        (every product rounded; nothing but the chains of G is fused)
+ *   ssim_px         = ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / (((mu1 * mu1 + mu2 * mu2) + C1) * ((s1 + s2) + C2))
+ *                     where pred == target over the whole window this is x / x == 1.0f exactly
+ *   map[b][y][x]    = (ssim_px of channel 0 + channel 1 + ...) / c       (optional: map may be NULL; rows w floats apart,
+ *                     samples map_bs floats apart)
+ *   ssim_c[b][ch]   = (float)(S / ((double)h * w)), S the sum of ssim_px over the channel's pixels (order below)
+ *   ssim[b]         = (float)(((double)ssim_c[b][0] + (double)ssim_c[b][1] + ...) / (double)c) from the STORED ssim_c:
+ *                     the reference's `ssim_error` on a batch of one
+ *   sq[b]           = the sum over the channels and pixels of (target - pred)^2 (order below).
+ *                     mse_error = 256 * sq / (c h w) (utils/utils.py:110-111); PSNR = 10 log10(4 c h w / sq) (the 4 is
+ *                     `psnr_error`'s halving of the difference)
+ * Order.  The frame is cut into tiles of ammc_ssim_tile() x ammc_ssim_tile() pixels anchored at (0, 0), the last tile row
+ * / column ragged; pixels of a tile past the frame's edge enter its sums as 0.  Within a tile a thread owns one column
+ * and 4 consecutive rows: (v0 + v1) + (v2 + v3), for d^2 then the channels in order; the 64 threads of a wave (32 columns
+ * x 2 groups of 4 rows) meet in a fixed xor tree (offsets 1, 2, .. 32); the 4 waves are added in order.  Each tile leaves
+ * c + 1 partials in workspace[(b * tiles + tile) * (c + 1) + k]; the second launch adds a sample's partials k in double
+ * in tile order (row-major) and rounds once.  Two launches, no atomics, no arrival counter, no allocation, no
+ * synchronisation: the same bits on every launch, and the order in which a tile's terms are added depends on
+ * (c, rows, cols) of that tile only - not on the sample's place in the batch, the batch size, the strides or the
+ * alignment (16-byte loads where all bases and strides allow, 4-byte loads otherwise; both fill the same LDS words in
+ * front of the same arithmetic), nor on whether map was asked for.  Non-finite inputs propagate into the outputs of
+ * their sample and into no other's.
+ * workspace: at least ammc_ssim_workspace_floats(batch, c, h, w) = batch * tiles * (c + 1) floats, owned by the call
+ * until its launches have run (one per stream).
+ * AMMC_EINVAL: a null pointer other than map; batch, c, h or w <= 0; pointers not 4-byte aligned; a row stride < w;
+ * a channel / batch stride smaller than the extent below it; map_bs < h * w with map given; workspace_floats smaller
+ * than the query's value.
+ * AMMC_EUNSUP: c > 4; batch * tiles >= 2^31 (the grid's x dimension; element offsets are 64-bit).
+ * All of them are decided before any HIP call and before win is read.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_ssim_tile(void);
+/* batch * ceil(h / tile) * ceil(w / tile) * (c + 1); 0 for non-positive arguments */
+int64_t ammc_ssim_workspace_floats(int32_t batch, int32_t c, int32_t h, int32_t w);
+int ammc_ssim_f32(const float* pred, int64_t p_bs, int64_t p_cs, int64_t p_rs, const float* target, int64_t t_bs,
+                  int64_t t_cs, int64_t t_rs, int32_t batch, int32_t c, int32_t h, int32_t w, const float* win, float* ssim,
+                  float* ssim_c, float* sq, float* map, int64_t map_bs, float* workspace, int64_t workspace_floats,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
