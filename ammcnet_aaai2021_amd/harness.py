@@ -1148,6 +1148,131 @@ def fuse_scores_auc(records: dict, gt: Sequence[np.ndarray], lam=None) -> dict:
     return {"auc": round(auc, 3), "auc_raw": auc, "lam": (l1, l2), "scores": smooth}
 
 
+# ---- score-fusion sweep: the AUC over a grid of channel weights and smoothings (DESIGN.md section 5.20) ----
+
+# channel name -> (key of the records dict, orientation).  Every channel enters the fusion as "higher = more normal":
+#   "img":  a quality of the prediction (PSNR, SSIM), used as `_minmax_concat` returns it
+#   "comm": a distance to the memory (commit records), used as 1.0f - n, as `fuse_scores_auc` uses the commit records
+#   "mse":  an error, negated BEFORE the normalisation (as run_quality's auc_mse), then as "img"
+FUSION_CHANNELS = {
+    "rgb_img_pred": ("rgb_img_pred_records", "img"), "op_img_pred": ("op_img_pred_records", "img"),
+    "rgb_fea_comm": ("rgb_fea_comm_records", "comm"), "op_fea_comm": ("op_fea_comm_records", "comm"),
+    "rgb_ssim": ("rgb_ssim_records", "img"), "op_ssim": ("op_ssim_records", "img"),
+    "rgb_mse": ("rgb_mse_records", "mse"), "op_mse": ("op_mse_records", "mse"),
+    "rgb_clip_comm": ("rgb_clip_comm_records", "comm"), "op_clip_comm": ("op_clip_comm_records", "comm"),
+    "rgb_patch_psnr": ("rgb_patch_psnr_records", "img"),
+}
+FUSION_LAM_FEA = [x * 0.01 for x in range(0, 100)]       # lam_rgb_fea_comm_list, main/eval_metric.py:422
+FUSION_LAM_SMOOTH = [x * 0.05 for x in range(0, 20)]     # lam_smooth_list, main/eval_metric.py:423
+
+
+def smoothing_pairs(lam_smooth: Sequence[float]) -> np.ndarray:
+    """[S, 2] fp32 pairs (a, b) = (float32(1 - l2), float32(l2)): the constants `fuse_scores_auc`'s fp32 arrays are
+    multiplied by"""
+    return np.array([[1 - l2, l2] for l2 in lam_smooth], dtype=np.float32).reshape(-1, 2)
+
+
+def fusion_grid(k: int = 2, step: Optional[float] = None) -> dict:
+    """The grid of a sweep over `k` channels: `weights` fp32 [G, k], `lam_smooth` (the reference's 20 values) and
+    `smooth`, their fp32 pairs.  k = 2 without a step: the reference's grid, `lam_fea` = x * 0.01 for x < 100 with the
+    weights (float32(1 - l1), float32(l1)).  Otherwise every vector whose entries are multiples of `step` (default 0.1)
+    and sum to 1, in lexicographic order, each entry float32(m / M) with M = round(1 / step)."""
+    if k < 1:
+        raise ValueError("fusion_grid: k >= 1")
+    out = {"lam_smooth": list(FUSION_LAM_SMOOTH), "smooth": smoothing_pairs(FUSION_LAM_SMOOTH)}
+    if k == 2 and step is None:
+        out["lam_fea"] = list(FUSION_LAM_FEA)
+        out["weights"] = np.array([[1 - l1, l1] for l1 in FUSION_LAM_FEA], dtype=np.float32)
+        return out
+    M = int(round(1.0 / (0.1 if step is None else step)))
+    if M < 1:
+        raise ValueError("fusion_grid: 0 < step <= 1")
+
+    def parts(left: int, slots: int):
+        if slots == 1:
+            yield (left,)
+            return
+        for m in range(left + 1):
+            for rest in parts(left - m, slots - 1):
+                yield (m,) + rest
+    out["weights"] = np.array([[m / M for m in v] for v in parts(M, k)], dtype=np.float32)
+    return out
+
+
+def fusion_channels(records: dict, channels: Sequence[str]) -> np.ndarray:
+    """fp32 [K, N]: the named channels of `records`, normalised (`_minmax_concat`: the first DECIDABLE_IDX frames of each
+    video dropped) and oriented so that higher = more normal (FUSION_CHANNELS)"""
+    rows = []
+    for name in channels:
+        if name not in FUSION_CHANNELS:
+            raise ValueError(f"unknown fusion channel {name!r}: one of {sorted(FUSION_CHANNELS)}")
+        key, kind = FUSION_CHANNELS[name]
+        if key not in records:
+            raise ValueError(f"fusion channel {name!r} needs records[{key!r}]: this evaluation did not compute it")
+        rec = records[key]
+        if kind == "mse":
+            rec = [-np.asarray(r, dtype=np.float32) for r in rec]
+        n = _minmax_concat(rec)
+        rows.append(1.0 - n if kind == "comm" else n)
+    return np.stack(rows).astype(np.float32, copy=False)
+
+
+def sweep_fusion(records: dict, gt: Sequence[np.ndarray], channels: Sequence[str] = ("rgb_img_pred", "rgb_fea_comm"),
+                 weights=None, smooth: Optional[Sequence[float]] = None, device=None) -> dict:
+    """The frame-level AUC of the fused score at every point of a grid, from one device launch (`ops.fusion_sweep`).
+    `records` / `gt` as `fuse_scores_auc` takes them; `channels`: names of FUSION_CHANNELS (at most 8); `weights`:
+    [G, K] (default `fusion_grid(K)`'s); `smooth`: lam_smooth values (default the reference's 20).  Returns `two_u`
+    (int64 [G, S]), `auc` (float64 [G, S] = two_u / (2 P Q)), `n_pos`, `n_neg`, `weights`, `lam_smooth`, `sweep_ms`
+    (the launch between device events), `best` = {weights, lam_smooth, auc, index} - on equal AUC the first in grid
+    order - and, for two channels of a dataset in LAM_MAP, `auc_at_lam_map`: the AUC at the published pair, which for
+    the default channels is `fuse_scores_auc`'s.  The HIP pass is the only implementation: a GPU is required."""
+    from . import ops
+    channels = tuple(channels)
+    chan = fusion_channels(records, channels)
+    labels = np.concatenate([np.asarray(g)[DECIDABLE_IDX:] for g in gt])
+    K, N = chan.shape
+    if labels.shape[0] != N:
+        raise ValueError(f"sweep_fusion: {labels.shape[0]} labels for {N} scored frames")
+    if not np.isfinite(chan).all():
+        bad = [c for c, row in zip(channels, chan) if not np.isfinite(row).all()]
+        raise ValueError(f"sweep_fusion: non-finite normalised scores in {bad} (a constant record, or a NaN / inf in it)")
+    pos, neg = np.flatnonzero(labels == 0), np.flatnonzero(labels != 0)
+    if pos.size == 0 or neg.size == 0:
+        raise ValueError("sweep_fusion: the labels hold one class only: the AUC is undefined")
+    grid = fusion_grid(K)
+    w = grid["weights"] if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1, K))
+    lam_smooth = list(grid["lam_smooth"] if smooth is None else smooth)
+    sm = smoothing_pairs(lam_smooth)
+    lam = LAM_MAP.get(records.get("dataset")) if K == 2 else None
+    if lam is not None:                                   # one more grid point of a second, 1 x 1 launch
+        w_lam, sm_lam = np.array([[1 - lam[0], lam[0]]], dtype=np.float32), smoothing_pairs([lam[1]])
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(dev)
+    d_chan, d_pos, d_neg = up(chan, torch.float32), up(pos, torch.int32), up(neg, torch.int32)
+    d_w, d_sm = up(w, torch.float32), up(sm, torch.float32)
+    with torch.cuda.device(dev):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        d_u = ops.fusion_sweep(d_chan, d_pos, d_neg, d_w, d_sm)
+        t1.record()
+        d_lam = ops.fusion_sweep(d_chan, d_pos, d_neg, up(w_lam, torch.float32), up(sm_lam, torch.float32)) if lam else None
+        two_u = d_u.cpu().numpy()
+        ms = t0.elapsed_time(t1)
+    denom = 2.0 * float(pos.size) * float(neg.size)
+    auc = two_u.astype(np.float64) / denom
+    gi, si = np.unravel_index(int(np.argmax(auc)), auc.shape)
+    out = {"two_u": two_u, "auc": auc, "n_pos": int(pos.size), "n_neg": int(neg.size), "channels": channels, "weights": w,
+           "lam_smooth": lam_smooth, "sweep_ms": float(ms),
+           "best": {"weights": [float(x) for x in w[gi]], "lam_smooth": float(lam_smooth[si]), "auc": float(auc[gi, si]),
+                    "index": (int(gi), int(si))}}
+    if d_lam is not None:
+        out["auc_at_lam_map"] = float(int(d_lam.cpu()[0, 0]) / denom)
+        out["lam_map"] = tuple(lam)
+    return out
+
+
 def weights_init_normal(model: torch.nn.Module) -> None:
     """the reference's training-from-scratch init (utils/utils.py:328-334): Conv* ~ N(0, 0.02),
     BatchNorm2d gamma ~ N(1, 0.02), beta = 0; applied by class name exactly as there"""

@@ -301,6 +301,58 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, map: bool = False, out: dict 
     return res
 
 
+# ---- score-fusion sweep (csrc/fusion_sweep.hip) -----------------------------------------------
+
+FUSION_MAX_CHANNELS = 8
+FUSION_MAX_SORTED = 32768    # `ammc_fusion_sweep_max_sorted()`: the smaller class is sorted in one workgroup's LDS
+
+
+def fusion_sweep(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tensor, weights: torch.Tensor,
+                 smooth: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Twice the Mann-Whitney U statistic - the exact numerator of the frame-level AUC - of the fused, smoothed score at
+    every point of a grid (csrc/fusion_sweep.hip; the definition is in include/ammc_hip.h).  `chan` fp32 [K, N] on the
+    GPU, K <= 8, frame stride 1, any row stride: K normalised channels, higher = more normal, all finite (the caller
+    checks).  `pos_idx` / `neg_idx`: int32 device vectors, the frames of the positive (normal) class and the others, a
+    partition of 0 .. N - 1 (not checked here: that would wait for the device; an index outside [0, N) is clamped).
+    `weights` fp32 [G, K], `smooth` fp32 [S, 2] (the pairs (a, b)), both on the GPU.  Returns int64 [G, S] (`out`, when
+    given: contiguous int64 [G, S]); AUC = two_u / (2 P Q).  One launch on torch's current stream; an integer sum, so
+    the same values on every launch.  The smaller class may have at most FUSION_MAX_SORTED frames: ValueError beyond."""
+    if chan.dim() != 2 or chan.dtype != torch.float32:
+        raise ValueError(f"fusion_sweep: chan must be fp32 [K, N], got {chan.dtype} {tuple(chan.shape)}")
+    K, N = chan.shape
+    if not 1 <= K <= FUSION_MAX_CHANNELS or N < 2:
+        raise ValueError(f"fusion_sweep: 1 <= K <= {FUSION_MAX_CHANNELS} channels over N >= 2 frames, got K = {K}, N = {N}")
+    if chan.stride(1) != 1 or (K > 1 and chan.stride(0) < N):
+        raise ValueError("fusion_sweep: chan needs frame stride 1 and a row stride >= N")
+    dev = chan.device
+    for name, t in (("pos_idx", pos_idx), ("neg_idx", neg_idx)):
+        if t.dim() != 1 or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"fusion_sweep: {name} must be a contiguous int32 vector on {dev}")
+    P, Q = pos_idx.numel(), neg_idx.numel()
+    if P < 1 or Q < 1 or P + Q != N:
+        raise ValueError(f"fusion_sweep: both classes non-empty and P + Q == N, got P = {P}, Q = {Q}, N = {N}")
+    if weights.dim() != 2 or weights.shape[1] != K or weights.shape[0] < 1 or smooth.dim() != 2 or smooth.shape[1] != 2 \
+            or smooth.shape[0] < 1:
+        raise ValueError(f"fusion_sweep: weights [G, {K}] and smooth [S, 2], got {tuple(weights.shape)} and {tuple(smooth.shape)}")
+    for name, t in (("weights", weights), ("smooth", smooth)):
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"fusion_sweep: {name} must be contiguous fp32 on {dev}")
+    if min(P, Q) > FUSION_MAX_SORTED:
+        raise ValueError(f"fusion_sweep: the smaller class has {min(P, Q)} frames, the pass sorts at most "
+                         f"{FUSION_MAX_SORTED} (ammc_fusion_sweep_max_sorted) in a workgroup's LDS")
+    G, S = weights.shape[0], smooth.shape[0]
+    _need_cuda(chan)
+    if out is None:
+        out = torch.empty((G, S), device=dev, dtype=torch.int64)
+    elif tuple(out.shape) != (G, S) or out.dtype != torch.int64 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"fusion_sweep: out must be contiguous torch.int64 {(G, S)} on {dev}")
+    lib = _lib.load()
+    rs = chan.stride(0) if K > 1 else max(chan.stride(0), N)
+    _lib.check(lib.ammc_fusion_sweep_f32(_ptr(chan), rs, K, N, _ptr(weights), G, _ptr(smooth), S, _ptr(pos_idx), P,
+                                         _ptr(neg_idx), Q, _ptr(out), _stream(chan)), "fusion_sweep")
+    return out
+
+
 def _nhwc_strides(t: torch.Tensor):
     """(batch, row, pixel) strides of an NHWC view [B, h, w, C] for `ammc_memory_scores_f32`; a dimension of size 1 may
     carry any stride in torch - it is given the extent below it instead"""

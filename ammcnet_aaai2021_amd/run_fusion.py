@@ -1,0 +1,116 @@
+"""Score-fusion sweep entry: the frame-level AUC of the fused score over a grid of channel weights and smoothings, from
+one device launch - which combination of the evaluation's records separates normal from
+anomalous frames, and how far the published (lam_fea, lam_smooth) pair of `harness.LAM_MAP` is from the best one.  The
+records come from an evaluation run here (`run_quality`'s model and data options: the four reference records plus SSIM
+and MSE) or from a file written by `--save_records`.  Labels are required.  One JSON line: "channels", "grid" [G, S],
+"n_pos", "n_neg", "sweep_ms" (the launch between device events), "best" {weights, lam_smooth, auc, index}, "auc_best"
+and - for two channels - "auc_at_lam_map", for the default channels `fuse_scores_auc`'s AUC.  One GPU.
+
+    python -m ammcnet_aaai2021_amd.run_fusion --synthetic [--save_records REC.npz] [--out GRID.npz]
+    python -m ammcnet_aaai2021_amd.run_fusion --records REC.npz --channels rgb_img_pred,rgb_ssim,rgb_fea_comm,op_fea_comm
+    python -m ammcnet_aaai2021_amd.run_fusion --data FILE.pt --ckpt model.pth --step 0.05 --channels ...
+"""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import torch
+
+from . import harness, parallel, pipeline, synthetic
+from .run_quality import build_parser as quality_parser
+from .run_test import synthetic_dataset, synthetic_raw_sources
+from .unet import get_twostream
+
+
+def build_parser():
+    p = quality_parser()
+    p.description = __doc__
+    p.add_argument("--records", default=None, help="sweep the records of a file written by --save_records (no model, no frames)")
+    p.add_argument("--save_records", default=None, help="write the evaluation's records, `lens` and `gt` to this .npz")
+    p.add_argument("--channels", default="rgb_img_pred,rgb_fea_comm",
+                   help="comma-separated names of harness.FUSION_CHANNELS (at most 8)")
+    p.add_argument("--step", type=float, default=None,
+                   help="weight step of the grid (default: the reference's 100 x 20 grid for two channels, 0.1 otherwise)")
+    p.add_argument("--out", default=None, help="write auc, two_u, weights and smooth to this .npz")
+    return p
+
+
+def flatten_records(rec: dict, gt) -> dict:
+    """the records dict as flat arrays: every `*_records` list concatenated, `lens` (frames per video) and `gt`"""
+    out = {k: np.concatenate([np.asarray(r, dtype=np.float32) for r in v]) for k, v in rec.items() if k.endswith("_records")}
+    out["lens"] = np.array([len(r) for r in rec["rgb_img_pred_records"]], dtype=np.int64)
+    out["gt"] = np.concatenate([np.asarray(g, dtype=np.int8) for g in gt])
+    return out
+
+
+def load_records(path: str, dataset_name: str):
+    """(records, gt) of a file in `flatten_records`' layout (tests/golden/score_fusion_ped2.npz has it)"""
+    with np.load(path) as d:
+        if "gt" not in d.files or "lens" not in d.files:
+            raise SystemExit(f"{path}: no `gt` / `lens`: the sweep needs frame labels")
+        cuts = np.cumsum(d["lens"])[:-1]
+        rec = {k: np.split(d[k], cuts) for k in d.files if k.endswith("_records")}
+        gt = np.split(d["gt"], cuts)
+    rec["dataset"] = dataset_name
+    return rec, gt
+
+
+def evaluate(a, dev):
+    model = get_twostream((12, 6), (3, 2), a.embed_dim, a.n_embed, a.k)
+    if a.ckpt:
+        model.load_state_dict(torch.load(a.ckpt, map_location="cpu"), strict=True)
+    else:
+        model.load_state_dict(synthetic.make_twostream_state(embed_dim=a.embed_dim, n_embed=a.n_embed, k=a.k))
+    model = model.to(dev).eval()
+    model.precision = a.precision
+    streamed = bool(a.rgb_root and a.op_root or (a.synthetic and a.raw))
+    if a.data:
+        blob = torch.load(a.data, map_location="cpu")
+        sources, gt = blob["videos"], blob.get("gt")
+    elif a.rgb_root and a.op_root:
+        sources, gt = pipeline.list_subvideos(a.rgb_root, a.op_root), None
+    elif a.synthetic and a.raw:
+        sources, gt = synthetic_raw_sources(a.videos, a.frames)
+    elif a.synthetic:
+        sources, gt = synthetic_dataset(a.videos, a.frames, a.size)
+    else:
+        raise SystemExit("give --records, --data, --rgb_root/--op_root or --synthetic")
+    if gt is None:
+        raise SystemExit("run_fusion needs frame labels: this data source has none (use --data with 'gt', or --records)")
+    if streamed:
+        sources = pipeline.SubVideoStager(sources, dev, size=(a.size, a.size), shard=(0, 1), ahead=2)
+    return harness.evaluate_dataset_quality(model, sources, a.dataset_name, False, device=dev), gt
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.maps_dir or a.ssim_maps:
+        raise SystemExit("run_fusion writes no maps: --maps_dir / --ssim_maps belong to run_quality")
+    channels = tuple(c.strip() for c in a.channels.split(",") if c.strip())
+    _, world, dev = parallel.init_distributed()
+    if world > 1:
+        raise SystemExit("run_fusion runs on one GPU (start a single process)")
+    if dev.type != "cuda":
+        raise SystemExit("run_fusion needs a GPU: the HIP path has no CPU fallback")
+    if a.records:
+        rec, gt = load_records(a.records, a.dataset_name)
+    else:
+        rec, gt = evaluate(a, dev)
+    if a.save_records:
+        np.savez(a.save_records, **flatten_records(rec, gt))
+    weights = None if a.step is None else harness.fusion_grid(len(channels), a.step)["weights"]
+    res = harness.sweep_fusion(rec, gt, channels, weights=weights, device=dev)
+    out = {"dataset": a.dataset_name, "channels": list(channels), "grid": list(res["auc"].shape), "n_pos": res["n_pos"],
+           "n_neg": res["n_neg"], "sweep_ms": round(res["sweep_ms"], 4), "best": res["best"], "auc_best": res["best"]["auc"]}
+    if "auc_at_lam_map" in res:
+        out["auc_at_lam_map"], out["lam_map"] = res["auc_at_lam_map"], list(res["lam_map"])
+    if a.out:
+        np.savez(a.out, auc=res["auc"], two_u=res["two_u"], weights=res["weights"],
+                 smooth=harness.smoothing_pairs(res["lam_smooth"]))
+        out["out"] = a.out
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -800,6 +800,47 @@ int ammc_ssim_f32(const float* pred, int64_t p_bs, int64_t p_cs, int64_t p_rs, c
                   float* ssim_c, float* sq, float* map, int64_t map_bs, float* workspace, int64_t workspace_floats,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Score-fusion sweep (csrc/fusion_sweep.hip): the exact numerator of the frame-level AUC of a weighted, one-tap-smoothed
+ * fusion of k score channels, at every point of a grid of g weight vectors x s smoothing pairs, from a pass of its own.
+ * (The reference fuses two channels at one published pair per dataset, main/eval_metric.py:382-439; the grids it
+ * defines at :422-423 are never iterated.)
+ *   chan     fp32 [k][n], rows chan_rs floats apart: k normalised score channels over the n scored frames in sequence
+ *            order; higher = more normal; all finite (the caller checks: a NaN has no place in an order)
+ *   w        fp32 [g][k]: the weight vectors
+ *   sm       fp32 [s][2]: the smoothing pairs (a, b); for the reference's lam_smooth l2 the caller passes
+ *            a = (float)(1 - l2), b = (float)l2
+ *   pos_idx  int32 [n_pos]: the frames of the positive class (the NORMAL class, label 0); neg_idx int32 [n_neg]: the
+ *            others.  Together a partition of 0 .. n - 1: n_pos + n_neg == n, n_pos, n_neg >= 1.  (An index outside
+ *            [0, n) is clamped into it: a meaningless count, never an access outside chan.)
+ * All five are DEVICE arrays.  For grid point (gi, si), with (a, b) = sm[si], every product and every sum a rounded fp32
+ * operation, nothing contracted into an FMA:
+ *   f[i]   = ((w[gi][0] * chan[0][i] + w[gi][1] * chan[1][i]) + w[gi][2] * chan[2][i]) + ...          left to right
+ *   t[0]   = f[0];   t[i] = a * f[i - 1] + b * f[i]  for i >= 1
+ *            from the UNSMOOTHED neighbour, across the whole concatenated sequence: the reference's smoothing does not
+ *            restart at a video boundary (eval_metric.py:427)
+ *   key[i] = t[i] + 0.0f             (-0.0 and +0.0 tie, as they do in an IEEE comparison)
+ *   two_u[gi][si] = sum over the positive p and the negative q of (2 * [key_p > key_q] + [key_p == key_q])
+ *            int64 [g][s], exact: twice the Mann-Whitney U statistic of the positives, ties counted half.
+ *   AUC    = two_u / (2.0 * n_pos * n_neg) in double, the caller's division: the area under the ROC curve with the
+ *            normal class positive, ties sharing one threshold (the trapezoid over distinct thresholds).
+ * With k = 2, w = ((float)(1 - l1), (float)l1) and chan = (img_n, 1.0f - fea_n) the keys are the scores of the
+ * reference's fusion bit for bit.
+ * One launch, one workgroup per grid point: the keys of the SMALLER class are sorted in LDS (a bitonic network over the
+ * next power of two, padded with a word above every finite key), every frame of the other class is located in the
+ * sorted array by two binary searches, and the workgroup adds the counts in int64.  An integer sum: no atomics, no
+ * arrival counter, nothing passes between workgroups, the same integers on every launch, in every grid, on every stream.
+ * Capacity: min(n_pos, n_neg) <= ammc_fusion_sweep_max_sorted() = 32768 (128 KiB of the CU's 160 KiB of LDS); n itself
+ * is bounded by int32 only.
+ * AMMC_EINVAL: a null pointer; k < 1 or k > 8; n < 2; g < 1 or s < 1; n_pos < 1 or n_neg < 1; n_pos + n_neg != n;
+ * chan_rs < n; chan, w, sm or an index list not 4-byte aligned, two_u not 8-byte aligned; min(n_pos, n_neg) over the
+ * capacity.  AMMC_EUNSUP: g * s >= 2^31 (the grid's x dimension).  All of them are decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_fusion_sweep_max_sorted(void);
+int ammc_fusion_sweep_f32(const float* chan, int64_t chan_rs, int32_t k, int32_t n, const float* w, int32_t g, const float* sm,
+                          int32_t s, const int32_t* pos_idx, int32_t n_pos, const int32_t* neg_idx, int32_t n_neg,
+                          int64_t* two_u, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
