@@ -1273,6 +1273,239 @@ def sweep_fusion(records: dict, gt: Sequence[np.ndarray], channels: Sequence[str
     return out
 
 
+# ---- pixel-level evaluation: mask-aware frame scores from the error maps ----
+# A pass of its own behind the evaluation forward and `ops.error_maps` (`ops.pixel_scores`, csrc/pixel_scores.hip): nothing
+# above is touched.  The pixel-level criterion (Mahadevan et al.) at the fraction num / den: a frame with ground-truth
+# pixels M is a true positive at threshold t iff at least num / den of M is detected (map >= t), a frame without ground
+# truth a false positive iff any pixel is.  With k = ceil(num |M| / den), "at least k of M are >= t" is "the k-th largest
+# value inside M is >= t", so the criterion's ROC over all thresholds is the frame-level ROC of ONE number per frame.
+
+def pixel_criterion_scores(m, kth, max_all):
+    """(scores, labels) of the pixel-level criterion, one per frame: `kth` and label 1 where the frame has ground-truth
+    pixels (m > 0), `max_all` and label 0 elsewhere.  numpy arrays; `roc_auc(labels, scores, pos_label=1)` is the area
+    under the criterion's ROC."""
+    m = np.asarray(m)
+    pos = m > 0
+    scores = np.where(pos, np.asarray(kth, dtype=np.float64), np.asarray(max_all, dtype=np.float64))
+    return scores, pos.astype(np.int8)
+
+
+def resize_mask(mask: torch.Tensor, size) -> torch.Tensor:
+    """Nearest-neighbour resize of a mask [..., h0, w0] to size = (H, W), any dtype, on the mask's device.  The rule,
+    in integers: target pixel (y, x) takes source pixel (floor((y + 0.5) * h0 / H), floor((x + 0.5) * w0 / W)) =
+    (((2 y + 1) * h0) // (2 H), ((2 x + 1) * w0) // (2 W)) - the pixel under the target pixel's centre.  Plain indexing:
+    a value of the result is a value of the source."""
+    if mask.dim() < 2:
+        raise ValueError("resize_mask: a mask [..., h0, w0]")
+    H, W = (int(v) for v in size)
+    h0, w0 = mask.shape[-2:]
+    if min(H, W, h0, w0) < 1:
+        raise ValueError(f"resize_mask: empty size {(h0, w0)} -> {(H, W)}")
+    ys = ((2 * torch.arange(H, device=mask.device) + 1) * h0) // (2 * H)
+    xs = ((2 * torch.arange(W, device=mask.device) + 1) * w0) // (2 * W)
+    return mask.index_select(-2, ys).index_select(-1, xs)
+
+
+def pool_mask(mask: torch.Tensor, patch: int) -> torch.Tensor:
+    """uint8 [..., ceil(H / patch), ceil(W / patch)] from a mask [..., H, W]: 1 where ANY pixel of the patch is nonzero,
+    over `ops.error_maps`' patch grid - patch x patch pixels anchored at (0, 0), the last row / column ragged."""
+    if mask.dim() < 2 or patch < 1:
+        raise ValueError("pool_mask: a mask [..., H, W] and a patch size >= 1")
+    lead, (h, w) = mask.shape[:-2], mask.shape[-2:]
+    any_px = (mask != 0).to(torch.float32).reshape(-1, 1, h, w)
+    pooled = torch.nn.functional.max_pool2d(any_px, kernel_size=patch, stride=patch, ceil_mode=True)
+    return pooled.to(torch.uint8).reshape(*lead, *pooled.shape[-2:])
+
+
+_PIXEL_KEYS = ("m", "kth", "max_in", "max_out")
+
+
+def pixel_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mask: torch.Tensor, patch: int = 16,
+                   frac=(2, 5), batch: int = EVAL_BATCH, keep_maps: bool = False) -> Dict[str, np.ndarray]:
+    """Is the error where the anomaly is: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W] and mask uint8 (or bool) [T,H,W]
+    (nonzero = anomalous, already at the frame size), contiguous and on the model's device -> per-frame numpy arrays of
+    the sub-video.  Behind every forward `ops.error_maps(rgb_pred, rgb_target, patch, pixel=True)` writes into one
+    per-batch buffer that every batch reuses, and `ops.pixel_scores` runs on its pixel map with the frames' masks and on
+    its patch means with `pool_mask(mask, patch)`: frame t's prediction meets mask[t].  Returned: `pix_m` (int32),
+    `pix_kth`, `pix_max_in`, `pix_max_out`, the same four with the prefix `patch_`, `rgb_psnr` (the fixed-order one of
+    `ops.error_maps`), `rgb_comm`, and for the record lists of the reference `op_psnr` (the output layer's epilogue) and
+    `op_comm`.  Only the rgb stream's maps are scored.  Clips, targets, batches, `defer_guard` and the `exact` re-run of
+    a flagged batch are `localise_subvideo`'s; frame indexing and fills are `assemble_records`' (`assemble_localised`):
+    the first RGB_LEN_CLIP - 1 frames repeat frame RGB_LEN_CLIP - 1's numbers.  The per-frame results lie in one flat
+    device buffer: one device-to-host copy per sub-video, and the frame-sized maps never leave the device - unless
+    `keep_maps`, a testing hook in the spirit of `predictions=`, asks for `pixel_map` [T,H,W] and `patch_map` [T,ph,pw]
+    as they were scored."""
+    from . import ops
+    t = rgb_frames.shape[0]
+    if op_frames.shape[0] != t - 1:
+        raise ValueError("a sub-video of T frames has T-1 flows")
+    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
+        raise ValueError("pixel_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
+    h, w = rgb_frames.shape[2:]
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != rgb_frames.device:
+        raise ValueError(f"pixel_subvideo: mask must be uint8 {(t, h, w)} on {rgb_frames.device}, got {mask.dtype} "
+                         f"{tuple(mask.shape)} on {mask.device}")
+    batches = subvideo_batches(t, batch)
+    if not batches:
+        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
+    mask = mask.contiguous()
+    pooled = pool_mask(mask, patch)
+    ph, pw = pooled.shape[1:]
+    n_clip = batches[-1][1]
+    dev = rgb_frames.device
+    sections = [(f"rgb_{g}_{key}", (n_clip,)) for g in ("pix", "patch") for key in _PIXEL_KEYS]
+    sections += [("rgb_psnr", (n_clip,)), ("op_psnr", (n_clip,))]
+    if keep_maps:
+        sections += [("rgb_pixel_map", (n_clip, h, w)), ("rgb_patch_map", (n_clip, ph, pw))]
+    sections += [("comm", (len(batches), 2)), ("flag", (len(batches),))]
+    slots = _FlatSlots(sections, ("rgb_pix_m", "rgb_patch_m"), dev)
+    bmax = max(e - s for s, e in batches)
+    buf = {"patch_sum": torch.empty((bmax, ph, pw), device=dev), "patch_mean": torch.empty((bmax, ph, pw), device=dev),
+           "pixel": torch.empty((bmax, h, w), device=dev), "frame_sq": torch.empty(bmax, device=dev),
+           "worst": torch.empty(bmax, device=dev), "worst_idx": torch.empty(bmax, device=dev, dtype=torch.int32)}
+
+    def run(k: int, exact: bool):
+        s, e = batches[k]
+        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
+        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
+        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        with torch.no_grad():
+            (rgb_out, _, diffs, _), _, op_psnr = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
+            flag = getattr(model, "last_overflow", None)
+            em = ops.error_maps(rgb_out, targets[0], patch, True, {key: v[:e - s] for key, v in buf.items()})
+            slots.view("rgb_psnr")[s:e] = em["psnr"]
+            slots.view("op_psnr")[s:e] = op_psnr
+            f0, f1 = s + RGB_LEN_CLIP - 1, e + RGB_LEN_CLIP - 1              # the frames these clips predict
+            for g, mp, mk in (("pix", em["pixel"], mask[f0:f1]), ("patch", em["patch_mean"], pooled[f0:f1])):
+                ops.pixel_scores(mp, mk, frac, {key: slots.view(f"rgb_{g}_{key}")[s:e] for key in _PIXEL_KEYS})
+            if keep_maps:
+                slots.view("rgb_pixel_map")[s:e] = em["pixel"]
+                slots.view("rgb_patch_map")[s:e] = em["patch_mean"]
+            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
+            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
+
+    for k in range(len(batches)):
+        run(k, False)
+    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
+    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
+    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
+        for k in flagged:
+            run(k, True)
+            _count_fallback(model)
+        host = slots.flat.cpu().numpy()
+    names = [n for n, _ in sections if n not in ("comm", "flag")]
+    parts = []
+    for k, (s, e) in enumerate(batches):
+        part = {n: slots.view(n, host)[s:e] for n in names}
+        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
+        parts.append(part)
+    rec = assemble_localised(t, batches, parts)
+    # (the rgb_ prefix chose the rgb stream's clip length in `assemble_localised`; the pixel figures carry none)
+    return {(k[4:] if k[4:].startswith(("pix", "patch_")) else k): v for k, v in rec.items()}
+
+
+def evaluate_dataset_pixel(model, videos, masks, dataset_name: str = "synthetic", patch: int = 16, frac=(2, 5), device=None,
+                           keep_maps: bool = False) -> dict:
+    """`evaluate_dataset` with `pixel_subvideo` in place of the scoring loop (one rank).  `videos`: as
+    `evaluate_dataset_localised` takes them.  `masks[v]`: the pixel ground truth of sub-video v, a uint8 / bool
+    [T, h0, w0] array or tensor at any resolution (uploaded and brought to the frame size with `resize_mask`, one
+    sub-video at a time), or None: such a sub-video is evaluated for the frame records and left out of every pixel
+    figure (the reference's `pixel_video_ids` subset).  A mask whose T differs from its video's raises ValueError.
+    Returns the four record lists of the reference (`rgb_img_pred_records` from the fixed-order PSNR), `n_frames`,
+    `mask_videos` (the indices of the sub-videos that have a mask) and per sub-video the per-frame arrays of
+    `pixel_subvideo` as lists by their names (`pix_m`, ..., `patch_max_out`; with `keep_maps` `pixel_map`, `patch_map`
+    and the resized `mask`), None at a sub-video without a mask."""
+    if device is None:
+        device = next(model.parameters()).device
+    keys = [f"{g}_{key}" for g in ("pix", "patch") for key in _PIXEL_KEYS] + (["pixel_map", "patch_map", "mask"] if keep_maps else [])
+    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
+           "op_fea_comm_records": [], "n_frames": [], "mask_videos": [], **{k: [] for k in keys}}
+    for v, (rgb, op) in enumerate(videos):
+        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+        t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
+        if v >= len(masks):
+            raise ValueError(f"evaluate_dataset_pixel: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
+        mk = masks[v]
+        if mk is None:
+            dm = torch.zeros((t, h, w), device=device, dtype=torch.uint8)
+        else:
+            mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
+            if mk.dim() != 3 or mk.shape[0] != t:
+                raise ValueError(f"evaluate_dataset_pixel: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
+            if mk.dtype not in (torch.uint8, torch.bool):
+                mk = mk != 0
+            dm = resize_mask(mk.to(device).view(torch.uint8) if mk.dtype == torch.bool else mk.to(device), (h, w)).contiguous()
+        rec = pixel_subvideo(model, rgb, op, dm, patch, frac, keep_maps=keep_maps and mk is not None)
+        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
+        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
+        out["op_img_pred_records"].append(rec["op_psnr"])
+        out["op_fea_comm_records"].append(rec["op_comm"])
+        out["n_frames"].append(t)
+        if mk is not None:
+            out["mask_videos"].append(v)
+            if keep_maps:
+                rec["mask"] = dm.cpu().numpy()
+        for k in keys:
+            out[k].append(rec[k] if mk is not None else None)
+    return out
+
+
+def pixel_level_auc(rec: dict, normalise: str = "none") -> dict:
+    """The pixel-level figures of `evaluate_dataset_pixel`'s result over its `mask_videos`, the first DECIDABLE_IDX
+    frames of each dropped, anomalous (a frame with ground-truth pixels) the positive class:
+      `auc_pixel`        the area under the pixel-level criterion's ROC on the pixel map: `roc_auc` of
+                         `pixel_criterion_scores` (exactly the criterion evaluated at every threshold)
+      `auc_pixel_patch`  the same on the patch map with the pooled masks
+      `auc_frame_max`    every frame scored by the largest value of its pixel map, wherever it lies
+      `pointing`         the share of anomalous frames whose largest value lies inside the mask (max_in >= max_out)
+      `n_anomalous`, `n_normal`
+    `normalise`: "none", or "video" - a sub-video's scores divided by its largest `max_all` (per map).  Selecting the
+    k-th largest commutes with a positive scale, so this is exactly the criterion on maps normalised per sub-video.
+    With an empty class the AUCs are None and `note` says why.  Non-finite scores raise ValueError: the kernel orders
+    bit patterns and leaves NaN to its caller."""
+    if normalise not in ("none", "video"):
+        raise ValueError(f"pixel_level_auc: normalise must be 'none' or 'video', got {normalise!r}")
+    cols = {"pix": ([], []), "patch": ([], []), "frame": ([], [])}
+    hits = []
+    for v in rec["mask_videos"]:
+        for g in ("pix", "patch"):
+            m = np.asarray(rec[f"{g}_m"][v])[DECIDABLE_IDX:]
+            kth, max_in, max_out = (np.asarray(rec[f"{g}_{key}"][v], dtype=np.float64)[DECIDABLE_IDX:]
+                                    for key in ("kth", "max_in", "max_out"))
+            max_all = np.maximum(max_in, max_out)
+            if g == "pix":
+                hits.append((max_in >= max_out)[m > 0])
+            if normalise == "video" and max_all.size and max_all.max() > 0:
+                c = max_all.max()
+                kth, max_all = kth / c, max_all / c
+            scores, labels = pixel_criterion_scores(m, kth, max_all)
+            cols[g][0].append(scores)
+            cols[g][1].append(labels)
+            if g == "pix":
+                cols["frame"][0].append(max_all)
+                cols["frame"][1].append(labels)
+    out = {"normalise": normalise}
+    cat = {g: (np.concatenate(s) if s else np.zeros(0), np.concatenate(lab) if lab else np.zeros(0, np.int8))
+           for g, (s, lab) in cols.items()}
+    labels = cat["pix"][1]
+    n_pos, n_neg = int((labels == 1).sum()), int((labels == 0).sum())
+    out["n_anomalous"], out["n_normal"] = n_pos, n_neg
+    for g, (scores, _) in cat.items():
+        if not np.isfinite(scores).all():
+            raise ValueError(f"pixel_level_auc: non-finite {g} scores (a NaN or an infinity in an error map)")
+    names = {"pix": "auc_pixel", "patch": "auc_pixel_patch", "frame": "auc_frame_max"}
+    if n_pos == 0 or n_neg == 0:
+        out.update({name: None for name in names.values()})
+        out["note"] = f"no {'anomalous' if n_pos == 0 else 'normal'} frame among the scored ones: the ROC has no area"
+    else:
+        for g, name in names.items():
+            out[name] = roc_auc(cat[g][1], cat[g][0], pos_label=1)
+    out["pointing"] = float(np.concatenate(hits).mean()) if n_pos else None
+    return out
+
+
 def weights_init_normal(model: torch.nn.Module) -> None:
     """the reference's training-from-scratch init (utils/utils.py:328-334): Conv* ~ N(0, 0.02),
     BatchNorm2d gamma ~ N(1, 0.02), beta = 0; applied by class name exactly as there"""

@@ -353,6 +353,68 @@ def fusion_sweep(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tenso
     return out
 
 
+# ---- pixel-level evaluation (csrc/pixel_scores.hip) -------------------------------------------
+
+PIXEL_MAX_PIXELS = 1 << 24   # h * w of one sample
+PIXEL_MAX_DEN = 4096
+
+
+def pixel_scores(map: torch.Tensor, mask: torch.Tensor, frac=(2, 5), out: dict | None = None) -> dict:
+    """What the pixel-level criterion needs of a score map and a ground-truth mask (csrc/pixel_scores.hip; definitions
+    in include/ammc_hip.h).  `map` fp32 [B, H, W] on the GPU, higher = more anomalous; `mask` uint8 or bool [B, H, W] on
+    the same device, nonzero = anomalous; each with contiguous samples and any batch stride >= H * W (nothing is copied).
+    `frac` = (num, den), 1 <= num <= den <= 4096.  Returns per sample `m` int32 [B] (mask pixels), `kth` (the k-th largest
+    map value inside the mask, k = ceil(num * m / den) in integers), `max_in`, `max_out` (the largest value inside /
+    outside the mask) - an empty set gives -inf - and the derived `max_all` = maximum(max_in, max_out).  The kernel does
+    no floating-point arithmetic: the floats are stored map values bit for bit, the same for a sample wherever it stands
+    in a batch.  NaN in the map is the caller's to keep out.  One launch on torch's current stream.  `out`: contiguous
+    [B] tensors to write into, by the keys `m`, `kth`, `max_in`, `max_out` (views of per-sub-video buffers)."""
+    if not isinstance(map, torch.Tensor) or not isinstance(mask, torch.Tensor) or map.dim() != 3 or mask.shape != map.shape:
+        raise ValueError("pixel_scores: map and mask must be [B, H, W] tensors of one shape")
+    if map.dtype != torch.float32 or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"pixel_scores: map must be fp32 and mask uint8 or bool, got {map.dtype} and {mask.dtype}")
+    B, H, W = map.shape
+    if B < 1 or H < 1 or W < 1 or H * W > PIXEL_MAX_PIXELS:
+        raise ValueError(f"pixel_scores: B, H, W >= 1 and H * W <= {PIXEL_MAX_PIXELS}, got {tuple(map.shape)}")
+    try:
+        num, den = (int(v) for v in frac)
+    except (TypeError, ValueError):
+        raise ValueError(f"pixel_scores: frac must be a pair (num, den), got {frac!r}") from None
+    if not 1 <= num <= den <= PIXEL_MAX_DEN:
+        raise ValueError(f"pixel_scores: 1 <= num <= den <= {PIXEL_MAX_DEN}, got {frac!r}")
+    for name, t in (("map", map), ("mask", mask)):
+        if not t[0].is_contiguous() or (B > 1 and t.stride(0) < H * W):
+            raise ValueError(f"pixel_scores: {name}: a sample must be contiguous, with a batch stride >= H * W")
+    if not map.is_cuda or mask.device != map.device:
+        raise ValueError("pixel_scores: map and mask must be on one GPU; there is no CPU fallback")
+    dev = map.device
+    out = dict(out) if out else {}
+    want = {"m": torch.int32, "kth": torch.float32, "max_in": torch.float32, "max_out": torch.float32}
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"pixel_scores: `out` has no slot {sorted(unknown)}")
+    res = {}
+    for key, dtype in want.items():
+        t = out.get(key)
+        if t is None:
+            t = torch.empty((B,), device=dev, dtype=dtype)
+        elif tuple(t.shape) != (B,) or t.dtype != dtype or t.device != dev:
+            raise ValueError(f"pixel_scores: out[{key!r}] must be {dtype} {(B,)} on {dev}")
+        elif not t.is_contiguous():
+            raise ValueError(f"pixel_scores: out[{key!r}] must be contiguous")
+        res[key] = t
+    lib = _lib.load()
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)                         # a bool is one byte, 0 or 1: the same memory
+    map_bs = max(map.stride(0), H * W) if B == 1 else map.stride(0)
+    mask_bs = max(mask.stride(0), H * W) if B == 1 else mask.stride(0)
+    _lib.check(lib.ammc_pixel_scores_f32(_ptr(map), map_bs, mask.data_ptr(), mask_bs, B, H, W, num, den,
+                                         res["m"].data_ptr(), _ptr(res["kth"]), _ptr(res["max_in"]), _ptr(res["max_out"]),
+                                         _stream(map)), "pixel_scores")
+    res["max_all"] = torch.maximum(res["max_in"], res["max_out"])
+    return res
+
+
 def _nhwc_strides(t: torch.Tensor):
     """(batch, row, pixel) strides of an NHWC view [B, h, w, C] for `ammc_memory_scores_f32`; a dimension of size 1 may
     carry any stride in torch - it is given the extent below it instead"""

@@ -1,0 +1,158 @@
+"""Pixel-level evaluation entry: `run_test`'s evaluation with the mask-aware pass behind the forward (DESIGN.md section
+5.21).  The same model, checkpoint and data-source options as `run_test`, plus pixel ground truth; one JSON line:
+`run_test`'s fields and the pixel-level figures of `harness.pixel_level_auc` - "auc_pixel" (the pixel-level criterion of
+Mahadevan et al. at the fraction --frac, on the per-pixel error map), "auc_pixel_patch" (the same on the patch map),
+"auc_frame_max", "pointing".  One GPU.
+
+    python -m ammcnet_aaai2021_amd.run_pixel --synthetic [--patch 8|16|32] [--frac 2 5] [--normalise none|video]
+    python -m ammcnet_aaai2021_amd.run_pixel --synthetic --raw                     # through the input pipeline
+    python -m ammcnet_aaai2021_amd.run_pixel --rgb_root DIR --op_root DIR --mask_root DIR   # the reference's folder layout
+    python -m ammcnet_aaai2021_amd.run_pixel --data blob.pt                        # its optional "masks" list
+
+Masks: `--data`: the blob's "masks", one uint8 [T, h0, w0] array (or None) per sub-video.  `--mask_root DIR`: files
+DIR/<sub-video folder name>.npy holding [T, h0, w0]; a sub-video without a file is scored for the frame records only
+(ped1 ships masks for a subset), a file that matches no sub-video is an error.  `--synthetic`: `synthetic_masks`.
+Masks may have any resolution: they are brought to the frame size by `harness.resize_mask` on the device.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import harness, parallel, pipeline, synthetic
+from .run_test import synthetic_dataset, synthetic_raw_sources
+from .unet import get_twostream
+
+RAW_SIZE = (240, 360)        # `run_test.synthetic_raw_sources`' camera resolution
+
+
+def synthetic_masks(n_videos: int, frames: int, h: int, w: int):
+    """deterministic stand-ins for pixel ground truth: uint8 [T, h, w] per sub-video with the lengths of
+    `run_test.synthetic_dataset` (frames + 7 * (i % 3)); about a fifth of the frames carry one rectangle of ones"""
+    out = []
+    for i in range(n_videos):
+        t = frames + 7 * (i % 3)
+        u = synthetic.hashed_uniform(f"rp:mask{i}", (t, 5), 0, 1).numpy()
+        mk = np.zeros((t, h, w), dtype=np.uint8)
+        for f in np.nonzero(u[:, 0] > 0.8)[0]:
+            rh, rw = 1 + int(u[f, 1] * (h // 2)), 1 + int(u[f, 2] * (w // 2))
+            y0, x0 = int(u[f, 3] * (h - rh + 1)), int(u[f, 4] * (w - rw + 1))
+            mk[f, y0:min(y0 + rh, h), x0:min(x0 + rw, w)] = 1
+        out.append(mk)
+    return out
+
+
+def masks_from_root(names, mask_root: str):
+    """`names`: the sub-video folder names in evaluation order -> [T, h0, w0] arrays read from mask_root/<name>.npy, None
+    where there is no such file; a .npy file that matches no sub-video raises ValueError"""
+    known = set(names)
+    stray = sorted(f for f in os.listdir(mask_root) if f.endswith(".npy") and f[:-4] not in known)
+    if stray:
+        raise ValueError(f"--mask_root {mask_root}: {stray} match no sub-video folder ({len(known)} folders)")
+    out = []
+    for name in names:
+        path = os.path.join(mask_root, name + ".npy")
+        out.append(np.load(path) if os.path.isfile(path) else None)
+    return out
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--patch", type=int, default=16, choices=(8, 16, 32), help="patch size of the patch map in pixels")
+    p.add_argument("--frac", type=int, nargs=2, default=[2, 5], metavar=("NUM", "DEN"),
+                   help="the share of the ground-truth pixels that must be detected (2 5: the 40 %% rule)")
+    p.add_argument("--normalise", default="none", choices=("none", "video"), help="divide a sub-video's scores by its largest value")
+    p.add_argument("--mask_root", default=None, help="with --rgb_root / --op_root: folder of <sub-video folder name>.npy masks [T,h,w]")
+    # the model and the data source, as run_test takes them
+    p.add_argument("--dataset_name", default="ped2", choices=sorted(harness.LAM_MAP))
+    p.add_argument("--ckpt", default=None, help="state_dict of the reference's twostream generator (.pth)")
+    p.add_argument("--data", default=None, help="torch.save'd dict with 'videos' and optional 'gt'")
+    p.add_argument("--synthetic", action="store_true")
+    p.add_argument("--raw", action="store_true", help="with --synthetic: uint8 frames + flows through pipeline.SubVideoStager")
+    p.add_argument("--rgb_root", default=None, help="folder of sub-video folders of frames (jpg/png/.npy)")
+    p.add_argument("--op_root", default=None, help="folder of sub-video folders of flows (.flo/.npy)")
+    p.add_argument("--videos", type=int, default=4)
+    p.add_argument("--frames", type=int, default=60)
+    p.add_argument("--size", type=int, default=256)
+    p.add_argument("--precision", choices=("fp32", "s16"), default="s16")
+    p.add_argument("--embed_dim", type=int, default=64)
+    p.add_argument("--n_embed", type=int, default=256)
+    p.add_argument("--k", type=int, default=2)
+    return p
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    num, den = a.frac
+    if not 1 <= num <= den <= 4096:
+        raise SystemExit(f"--frac NUM DEN needs 1 <= NUM <= DEN <= 4096, got {num} {den}")
+    _, world, dev = parallel.init_distributed()
+    if world > 1:
+        raise SystemExit("run_pixel runs on one GPU: sharded pixel-level evaluation is not implemented (start a single process)")
+    if dev.type != "cuda":
+        raise SystemExit("run_pixel needs a GPU: the HIP path has no CPU fallback")
+    model = get_twostream((12, 6), (3, 2), a.embed_dim, a.n_embed, a.k)
+    if a.ckpt:
+        model.load_state_dict(torch.load(a.ckpt, map_location="cpu"), strict=True)
+    else:
+        model.load_state_dict(synthetic.make_twostream_state(embed_dim=a.embed_dim, n_embed=a.n_embed, k=a.k))
+    model = model.to(dev).eval()
+    model.precision = a.precision
+    streamed = bool(a.rgb_root and a.op_root or (a.synthetic and a.raw))
+    if a.data:
+        blob = torch.load(a.data, map_location="cpu")
+        sources, gt, masks = blob["videos"], blob.get("gt"), blob.get("masks")
+        if masks is None:
+            raise SystemExit("--data: the blob has no 'masks' list (one [T,h,w] array or None per sub-video)")
+    elif a.rgb_root and a.op_root:
+        if not a.mask_root:
+            raise SystemExit("--rgb_root / --op_root need --mask_root DIR for the pixel ground truth")
+        sources, gt = pipeline.list_subvideos(a.rgb_root, a.op_root), None
+        try:
+            masks = masks_from_root(sorted(os.listdir(a.rgb_root)), a.mask_root)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+    elif a.synthetic and a.raw:
+        sources, gt = synthetic_raw_sources(a.videos, a.frames)
+        masks = synthetic_masks(a.videos, a.frames, *RAW_SIZE)
+    elif a.synthetic:
+        sources, gt = synthetic_dataset(a.videos, a.frames, a.size)
+        masks = synthetic_masks(a.videos, a.frames, a.size, a.size)
+    else:
+        raise SystemExit("give --data, --rgb_root/--op_root or --synthetic")
+    if len(masks) != len(sources):
+        raise SystemExit(f"{len(masks)} masks for {len(sources)} sub-videos")
+
+    def loop(srcs, mks):
+        # raw inputs stream: sub-video v + 1 / v + 2 are read, uploaded and resized on a side stream while v is scored
+        st = pipeline.SubVideoStager(srcs, dev, size=(a.size, a.size), shard=(0, 1), ahead=2) if streamed else None
+        rec = harness.evaluate_dataset_pixel(model, st if streamed else srcs, mks, a.dataset_name, a.patch, (num, den), device=dev)
+        return rec, st
+    loop(sources[:1], masks[:1])                                                 # warm-up: plans, packs, pinned pools
+    torch.cuda.synchronize()
+    t0 = time.time()
+    rec, st = loop(sources, masks)
+    torch.cuda.synchronize()
+    used = time.time() - t0
+    n_pred = sum(t - harness.RGB_LEN_CLIP + 1 for t in rec["n_frames"])
+    out = {"dataset": a.dataset_name, "videos": len(rec["n_frames"]), "predicted_frames": n_pred, "gpus": 1,
+           "total_time_s": round(used, 3), "fps": round(n_pred / used, 2), "precision": a.precision,
+           "s16_fallbacks": getattr(model, "s16_fallbacks", 0)}
+    if st is not None:
+        out.update(host_read_s=round(st.host_seconds, 3), uploaded_MB=round(st.bytes_uploaded / 2**20, 1),
+                   staging="streamed: overlapped with the pixel-level loop (total_time_s covers it)")
+    if gt is not None:
+        out["auc"] = harness.fuse_scores_auc(rec, gt)["auc"]
+    out.update(harness.pixel_level_auc(rec, a.normalise))
+    out.update(frac=[num, den], patch=a.patch, mask_videos=len(rec["mask_videos"]))
+    out["auc_note"] = "synthetic masks" if a.synthetic else ("masks from --data" if a.data else "masks from --mask_root")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -841,6 +841,35 @@ int ammc_fusion_sweep_f32(const float* chan, int64_t chan_rs, int32_t k, int32_t
                           int32_t s, const int32_t* pos_idx, int32_t n_pos, const int32_t* neg_idx, int32_t n_neg,
                           int64_t* two_u, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Pixel-level evaluation (csrc/pixel_scores.hip): what the pixel-level criterion of Mahadevan et al. needs of a score
+ * map and a ground-truth mask, per sample, from a pass of its own.
+ *   map      fp32 [batch][h][w], higher = more anomalous; a sample contiguous (h * w floats), samples map_bs floats apart
+ *   mask     uint8 [batch][h][w], nonzero = anomalous; a sample contiguous, samples mask_bs bytes apart
+ * Both are DEVICE arrays.  With M(b) the mask pixels of sample b:
+ *   m[b]        = |M(b)|
+ *   kth[b]      = the k-th largest map value over M(b), counted with multiplicity, k = (m * frac_num + frac_den - 1) /
+ *                 frac_den in int64 = ceil(frac_num * m / frac_den): at least the fraction frac_num / frac_den of M(b) is
+ *                 >= a threshold t exactly when kth[b] >= t.  (frac 1/1: the minimum over M(b); m * num <= den: max_in)
+ *   max_in[b]   = the largest value over M(b);  max_out[b] = the largest value over the pixels outside M(b)
+ *   an empty set gives -inf: kth and max_in where m == 0, max_out where m == h * w
+ * Every float output is one of the stored map values, bit for bit.  No floating-point operation touches a map value:
+ * every comparison is an unsigned comparison of key(bits) = bits has its sign bit ? ~bits : bits | 0x80000000, which
+ * orders all non-NaN values as their values do (-0.0 one step below +0.0), denormals and negative values included.  NaN
+ * is the CALLER's duty to keep out of the map: a NaN ranks by its key (above +inf or below -inf, by its sign) and
+ * nothing reports it; check the returned values for finiteness.
+ * One launch, one workgroup per sample: a radix select over the keys in three passes (11, 11 and 10 bits) that re-read
+ * the sample, integer histograms in LDS.  Plain stores, every output written once by one thread, nothing passes between
+ * workgroups, no global atomics: the outputs of sample b are a function of (map[b], mask[b], h * w, frac_num, frac_den)
+ * and of nothing else - not the batch size, the sample's place in the batch, a stride or an alignment (16-byte map
+ * loads and 4-byte mask loads where the bases and batch strides allow, 4-byte and 1-byte loads otherwise).
+ * AMMC_EINVAL: a null pointer; batch, h or w < 1; h * w > 2^24; frac_num < 1, frac_den < frac_num or frac_den > 4096;
+ * with batch > 1 a batch stride < h * w; map or an output not 4-byte aligned.  All decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_pixel_scores_f32(const float* map, int64_t map_bs, const uint8_t* mask, int64_t mask_bs, int32_t batch, int32_t h,
+                          int32_t w, int32_t frac_num, int32_t frac_den, int32_t* m, float* kth, float* max_in,
+                          float* max_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
