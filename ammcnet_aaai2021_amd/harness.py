@@ -1506,6 +1506,437 @@ def pixel_level_auc(rec: dict, normalise: str = "none") -> dict:
     return out
 
 
+# ---- qualitative evaluation: prediction, flow and error panels ------------------------------
+# A pass of its own behind the evaluation forward (`ops.render_panels`, csrc/render.hip): finished uint8 pictures of the
+# frames, the colour-coded flows and the error heat maps.  The scoring loops above are not touched.
+
+RENDER_TILES = ("rgb_target", "rgb_pred", "rgb_heat", "op_target", "op_pred", "op_heat")       # the C ABI's tile ids
+RENDER_DEFAULT_TILES = (RENDER_TILES[:3], RENDER_TILES[3:])
+FLOW_UNKNOWN = 1e7           # a flow component above it (or a NaN) marks a pixel without a flow (Middlebury's convention)
+
+
+def panel_layout(tiles) -> List[List[str]]:
+    """`tiles` as rows of tile names: a sequence of names is one row, a sequence of sequences the rows (equal lengths).
+    An ordered subset of RENDER_TILES - at most six, none twice.  ValueError otherwise."""
+    if isinstance(tiles, str):
+        tiles = [tiles]
+    rows = [list(tiles)] if all(isinstance(t, str) for t in tiles) else [[t for t in row] for row in tiles]
+    flat = [t for row in rows for t in row]
+    if not flat or any(len(row) != len(rows[0]) for row in rows):
+        raise ValueError(f"render: tiles must be a non-empty row of names or rows of equal length, got {tiles!r}")
+    for t in flat:
+        if t not in RENDER_TILES:
+            raise ValueError(f"render: unknown tile {t!r}; the tiles are {', '.join(RENDER_TILES)}")
+    if len(set(flat)) != len(flat):
+        raise ValueError(f"render: every tile at most once, got {flat}")
+    return rows
+
+
+def colour_wheel() -> np.ndarray:
+    """the Middlebury colour wheel [55, 3] as fp32 values / 255, from its published segment lengths: along a segment of
+    length n one channel holds 255 and one ramps floor(255 i / n) - up in the 1st, 3rd and 5th segment, down from 255 in
+    the others"""
+    wheel, k = np.zeros((55, 3), dtype=np.float32), 0
+    for s, (n, full, ramp) in enumerate(((15, 0, 1), (6, 1, 0), (4, 1, 2), (11, 2, 1), (13, 2, 0), (6, 0, 2))):
+        for i in range(n):
+            r = 255 * i // n
+            wheel[k, full] = 255
+            wheel[k, ramp] = r if s % 2 == 0 else 255 - r
+            k += 1
+    return wheel / np.float32(255)
+
+
+def _flow_parts(flow: np.ndarray, scale):
+    """fp32: the scaled components with the unknown pixels zeroed, the radius, the known mask; flow [B,2,H,W]"""
+    f32 = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        u, v = f32(scale[0]) * flow[:, 0].astype(f32), f32(scale[1]) * flow[:, 1].astype(f32)
+        known = (np.abs(u) <= f32(FLOW_UNKNOWN)) & (np.abs(v) <= f32(FLOW_UNKNOWN))         # False for a NaN
+    u, v = np.where(known, u, f32(0)), np.where(known, v, f32(0))
+    return u, v, np.sqrt(u * u + v * v), known
+
+
+def flow_colour_reference(flow, scale=(1.0, 1.0), max_rad=None) -> Dict[str, np.ndarray]:
+    """The Middlebury colour code of flows [B,2,H,W] (tensor or array, any device) in fp32 numpy, as include/ammc_hip.h
+    defines it: `rgb` uint8 [B,H,W,3], `raw` [B,H,W] (the radius), `max_rad` [B] (each sample's largest radius, or the
+    supplied per-sample values), `inside` and `known` [B,H,W].  The reference's `flow_to_image` up to one deliberate
+    difference: a pixel is inside when raw <= max_rad and its normalised radius is clamped to 1 (the reference re-derives
+    the radius from the normalised components in float64, which lands on either side of 1 for the pixels that attain the
+    maximum)."""
+    f32 = np.float32
+    flow = flow.detach().cpu().numpy() if isinstance(flow, torch.Tensor) else np.asarray(flow)
+    u, v, raw, known = _flow_parts(flow, scale)
+    own = raw.reshape(raw.shape[0], -1).max(axis=1)
+    if max_rad is None:
+        mr = own
+    else:
+        mr = (max_rad.detach().cpu().numpy() if isinstance(max_rad, torch.Tensor) else np.asarray(max_rad)).astype(f32)
+    mr3 = mr.astype(f32)[:, None, None]
+    with np.errstate(over="ignore"):
+        inv = f32(1) / (mr3 + f32(2.0 ** -52))
+        inside = raw <= mr3
+        rad = np.minimum(raw * inv, f32(1))
+    a = np.arctan2(-v, -u) / f32(np.pi)
+    fk = (a + f32(1)) / f32(2) * f32(54) + f32(1)
+    k0f = np.clip(np.floor(fk), f32(1), f32(55))
+    k0 = k0f.astype(np.int64)
+    k1 = np.where(k0 == 55, 1, k0 + 1)
+    f = fk - k0f
+    wheel = colour_wheel()
+    out = np.zeros(raw.shape + (3,), dtype=np.uint8)
+    for ch in range(3):
+        col = (f32(1) - f) * wheel[k0 - 1, ch] + f * wheel[k1 - 1, ch]
+        col = np.where(inside, f32(1) - rad * (f32(1) - col), col * f32(0.75))
+        out[..., ch] = np.where(known, np.clip(np.floor(f32(255) * col), 0, 255), 0).astype(np.uint8)
+    return {"rgb": out, "raw": raw, "max_rad": mr.astype(f32), "own_max": own, "inside": inside, "known": known}
+
+
+def _err32(pred: np.ndarray, target: np.ndarray) -> np.ndarray:
+    """fp32 `ops.error_maps` pixel: ((d_0^2 + d_1^2) + ...) / c with d = 0.5 (target - pred); a NaN counts as 0"""
+    f32 = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        acc = None
+        for ch in range(pred.shape[1]):
+            d = f32(0.5) * (target[:, ch] - pred[:, ch])
+            acc = d * d if acc is None else acc + d * d
+        e = acc / f32(pred.shape[1])
+    return np.where(np.isnan(e), f32(0), e)
+
+
+def frame_tile_reference(x: np.ndarray) -> np.ndarray:
+    """float64: u8 = floor(clamp((x + 1) * 127.5, 0, 255) + 0.5) per channel, [B,3,H,W] -> uint8 [B,H,W,3]; NaN -> 0"""
+    x = np.where(np.isnan(x), -1.0, x.astype(np.float64))
+    return np.floor(np.clip((x + 1.0) * 127.5, 0.0, 255.0) + 0.5).astype(np.uint8).transpose(0, 2, 3, 1)
+
+
+def heat_tile_reference(e: np.ndarray, heat_max: np.ndarray, grey: np.ndarray, alpha: float) -> np.ndarray:
+    """float64: t = min(e / heat_max, 1) (0 where heat_max <= 0), colour = clamp(1.5 - |4 t - (3, 2, 1)|, 0, 1),
+    u8 = floor((1 - alpha) * grey + alpha * 255 * colour + 0.5); e [B,H,W], heat_max [B], grey [B,H,W] or a number"""
+    hm = np.asarray(heat_max, dtype=np.float64)[:, None, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(hm > 0, np.minimum(np.nan_to_num(e.astype(np.float64) / hm, nan=1.0), 1.0), 0.0)
+    a = float(np.float32(alpha))
+    grey = np.broadcast_to(np.asarray(grey, dtype=np.float64), e.shape)
+    out = np.empty(e.shape + (3,), dtype=np.uint8)
+    for ch in range(3):
+        c = np.clip(1.5 - np.abs(4.0 * t - (3 - ch)), 0.0, 1.0)
+        out[..., ch] = np.clip(np.floor((1.0 - a) * grey + a * 255.0 * c + 0.5), 0, 255).astype(np.uint8)
+    return out
+
+
+def render_reference(rgb_pred, rgb_target, op_pred, op_target, tiles=RENDER_DEFAULT_TILES, flow_scale=(1.0, 1.0),
+                     flow_norm="target", heat_max="frame", alpha: float = 0.6) -> Dict[str, np.ndarray]:
+    """The quantities of `ops.render_panels` in plain numpy (tensors of any device or arrays; the witness of the tests):
+    the colour code in fp32 (`flow_colour_reference`), the frame and heat tiles in float64.  The normalising maxima
+    (`stats` [B,4] fp32: the largest radius of the target and of the predicted flow, the largest per-pixel error of the
+    frame pair and of the flow pair) are the fp32 restatement the kernel must reproduce bit for bit.  Returns `panels`
+    uint8 [B, rows*H, cols*W, 3], `stats`, and every tile by its name [B,H,W,3]."""
+    f32 = np.float32
+    arr = [t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (rgb_pred, rgb_target, op_pred, op_target)]
+    rp, rt, fp, ft = (a.astype(f32) for a in arr)
+    rows = panel_layout(tiles)
+    b = rp.shape[0]
+    ct, cp = flow_colour_reference(ft, flow_scale), flow_colour_reference(fp, flow_scale)
+    e_rgb64 = (((rt.astype(np.float64) - rp.astype(np.float64)) * 0.5) ** 2).mean(axis=1)
+    e_op64 = (((ft.astype(np.float64) - fp.astype(np.float64)) * 0.5) ** 2).mean(axis=1)
+    both = ct["known"] & cp["known"]
+    e_rgb64 = np.where(np.isnan(e_rgb64), 0.0, e_rgb64)
+    e_op64 = np.where(both & ~np.isnan(e_op64), e_op64, 0.0)
+    e_op32 = np.where(both, _err32(fp, ft), f32(0))
+    stats = np.stack([ct["own_max"], cp["own_max"], _err32(rp, rt).reshape(b, -1).max(axis=1),
+                      e_op32.reshape(b, -1).max(axis=1)], axis=1).astype(f32)
+
+    def vec(v):
+        return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(f32).reshape(b)
+    if isinstance(flow_norm, str):
+        if flow_norm not in ("target", "each"):
+            raise ValueError(f"render: flow_norm must be 'target', 'each' or a tensor [B], got {flow_norm!r}")
+        mr_t, mr_p = stats[:, 0], (stats[:, 0] if flow_norm == "target" else stats[:, 1])
+    else:
+        mr_t = mr_p = vec(flow_norm)
+    if isinstance(heat_max, str):
+        if heat_max != "frame":
+            raise ValueError(f"render: heat_max must be 'frame', a tensor [B] or a pair of them, got {heat_max!r}")
+        hm_rgb, hm_op = stats[:, 2], stats[:, 3]
+    elif isinstance(heat_max, (tuple, list)):
+        hm_rgb, hm_op = vec(heat_max[0]), vec(heat_max[1])
+    else:
+        hm_rgb = hm_op = vec(heat_max)
+    out = {"stats": stats}
+    out["rgb_target"], out["rgb_pred"] = frame_tile_reference(rt), frame_tile_reference(rp)
+    out["rgb_heat"] = heat_tile_reference(e_rgb64, hm_rgb, out["rgb_target"].astype(np.float64).sum(axis=3) / 3.0, alpha)
+    out["op_target"] = flow_colour_reference(ft, flow_scale, mr_t)["rgb"]
+    out["op_pred"] = flow_colour_reference(fp, flow_scale, mr_p)["rgb"]
+    out["op_heat"] = heat_tile_reference(e_op64, hm_op, 128.0, alpha)
+    out["panels"] = np.concatenate([np.concatenate([out[t] for t in row], axis=2) for row in rows], axis=1)
+    return out
+
+
+def render_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, select=None, tiles=RENDER_DEFAULT_TILES,
+                    flow_scale=None, flow_norm="target", heat_max="frame", alpha: float = 0.6, batch: int = EVAL_BATCH,
+                    ring: int = 2, stats: Optional[dict] = None):
+    """Pictures of a sub-video: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and on the model's device ->
+    a generator of (frame index, panel uint8 [rows*H, cols*W, 3]) in frame order.  Frame f >= RGB_LEN_CLIP - 1 is the
+    target of clip f - (RGB_LEN_CLIP - 1), with flow f - 1 the target of the flow stream: `localise_subvideo`'s clips,
+    targets, batches (`batch` clips at a time), `defer_guard` and `exact` re-run of a batch whose S16 range flag is set.
+    `select`: the frame indices to render (any iterable; default every predicted frame) - only the batches that hold one
+    run, and of such a batch only the span of clips between its first and last selected one is rendered and copied.
+    Behind the forward `ops.render_panels` writes the span's panels into a device buffer, whose last word receives the
+    range flag; ONE device-to-host copy per batch on a side stream brings both into a pinned ring of `ring` buffers
+    while the next batch runs.  The yielded panel is the caller's own array (a copy out of the ring).
+    `flow_scale`: default (H, W), the reference's `get_vis_tensor` re-scaling.  The other options are `ops.render_panels`'.
+    `stats` (optional dict) receives `render_ms` (the render launches between events, summed), `render_batches`,
+    `copies`, `rerun_batches`."""
+    from . import ops
+    t = rgb_frames.shape[0]
+    if op_frames.shape[0] != t - 1:
+        raise ValueError("a sub-video of T frames has T-1 flows")
+    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
+        raise ValueError("render_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
+    batches = subvideo_batches(t, batch)
+    if not batches:
+        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
+    lc = RGB_LEN_CLIP - 1
+    if select is None:
+        clips = list(range(batches[-1][1]))
+    else:
+        frames = sorted(set(int(f) for f in select))
+        if frames and (frames[0] < lc or frames[-1] >= t):
+            raise ValueError(f"render_subvideo: the predicted frames are {lc} .. {t - 1}, got {frames[0]} .. {frames[-1]}")
+        clips = [f - lc for f in frames]
+    rows = panel_layout(tiles)
+    h, w = rgb_frames.shape[2:]
+    if flow_scale is None:
+        flow_scale = (float(h), float(w))
+    ph, pw = len(rows) * h, len(rows[0]) * w
+    per = ph * pw * 3
+    dev = rgb_frames.device
+    work = []                                                       # (batch index, first clip, last clip + 1, wanted clips)
+    for k, (s, e) in enumerate(batches):
+        mine = [c for c in clips if s <= c < e]
+        if mine:
+            work.append((k, mine[0], mine[-1] + 1, mine))
+    if not work:
+        return
+    head = 16                                                       # the range flag's word, in front of the panels
+    cap = head + max(hi - lo for _, lo, hi, _ in work) * per
+    ring = max(int(ring), 2)
+    dbuf = [torch.empty(cap, device=dev, dtype=torch.uint8) for _ in range(ring)]
+    hbuf = [torch.empty(cap, dtype=torch.uint8, pin_memory=True) for _ in range(ring)]
+    side = torch.cuda.Stream(device=dev)
+    timed, copies, reruns = [], 0, 0
+    # a number in place of a mode: the same value for every frame (pictures of different frames are then comparable)
+    fixed = {key: torch.full((batch,), float(v), device=dev, dtype=torch.float32)
+             for key, v in (("flow_norm", flow_norm), ("heat_max", heat_max)) if isinstance(v, (int, float))}
+
+    def launch(j: int, exact: bool):
+        k, lo, hi, _ = work[j]
+        s, e = batches[k]
+        slot = j % ring
+        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
+        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
+        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        with torch.no_grad():
+            (rgb_out, op_out, _, _), *_ = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
+            flag = getattr(model, "last_overflow", None)
+            n = hi - lo
+            out = dbuf[slot][head:head + n * per].view(n, ph, pw, 3)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            ops.render_panels(rgb_out[lo - s:hi - s], targets[0][lo - s:hi - s], op_out[lo - s:hi - s], targets[1][lo - s:hi - s],
+                              tiles=rows, flow_scale=flow_scale, alpha=alpha, out=out,
+                              flow_norm=fixed["flow_norm"][:n] if "flow_norm" in fixed else flow_norm,
+                              heat_max=fixed["heat_max"][:n] if "heat_max" in fixed else heat_max)
+            ev1.record()
+            timed.append((ev0, ev1))
+            word = dbuf[slot][:4].view(torch.float32)
+            if flag is not None:
+                word.copy_(flag.reshape(1).to(torch.float32))
+            else:
+                word.zero_()
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            hbuf[slot][:head + n * per].copy_(dbuf[slot][:head + n * per], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(side)
+        return done
+
+    def finish(j: int, done):
+        nonlocal reruns, copies
+        k, lo, hi, mine = work[j]
+        slot = j % ring
+        done.synchronize()
+        copies += 1
+        host = hbuf[slot].numpy()
+        if host[:4].view(np.float32)[0] != 0:                        # S16 range guard: this batch again on the exact-fp32 kernels
+            launch(j, True).synchronize()
+            copies += 1
+            reruns += 1
+            _count_fallback(model)
+        panels = host[head:head + (hi - lo) * per].reshape(hi - lo, ph, pw, 3)
+        return [(c + lc, panels[c - lo].copy()) for c in mine]
+
+    try:
+        pending = None
+        for j in range(len(work)):
+            # batch j runs while the copy of batch j - 1 is in flight; buffer j % ring is free: the copy of batch
+            # j - ring (<= j - 2) was awaited when that batch was handed out
+            done = launch(j, False)
+            if pending is not None:
+                yield from finish(*pending)
+            pending = (j, done)
+        if pending is not None:
+            yield from finish(*pending)
+    finally:
+        torch.cuda.current_stream(dev).wait_stream(side)
+        if stats is not None:
+            torch.cuda.synchronize(dev)
+            stats["render_ms"] = stats.get("render_ms", 0.0) + sum(a.elapsed_time(b) for a, b in timed)
+            stats["render_batches"] = stats.get("render_batches", 0) + len(timed)
+            stats["copies"] = stats.get("copies", 0) + copies
+            stats["rerun_batches"] = stats.get("rerun_batches", 0) + reruns
+
+
+class OrderedWriterPool:
+    """A bounded pool of writer threads: `submit(fn, *args)` queues a job (it blocks while 2 x workers jobs are waiting:
+    the producer cannot run ahead of the disk), `close()` hands the return values back in SUBMISSION order.
+    The first exception of a job is raised by the next `submit` or by `close` - never lost - and the jobs queued behind it
+    are dropped."""
+
+    MAX_WORKERS = 16
+
+    def __init__(self, workers: int = 8):
+        from concurrent.futures import ThreadPoolExecutor
+        import threading
+        if workers < 1:
+            raise ValueError(f"OrderedWriterPool: at least one worker, got {workers}")
+        self.workers = min(int(workers), self.MAX_WORKERS)
+        self._pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="panel-writer")
+        self._room = threading.BoundedSemaphore(2 * self.workers)
+        self._futures = []
+        self._checked = 0
+        self.busy_s = 0.0                                           # seconds the jobs ran, summed over the threads
+        self._lock = threading.Lock()
+
+    def _run(self, fn, args):
+        import time
+        t0 = time.perf_counter()
+        try:
+            return fn(*args)
+        finally:
+            with self._lock:
+                self.busy_s += time.perf_counter() - t0
+            self._room.release()
+
+    def _raise_finished(self):
+        while self._checked < len(self._futures) and self._futures[self._checked].done():
+            self._futures[self._checked].result()                   # raises the job's exception
+            self._checked += 1
+
+    def submit(self, fn, *args) -> None:
+        try:
+            self._raise_finished()
+        except BaseException:
+            self._abort()
+            raise
+        self._room.acquire()
+        self._futures.append(self._pool.submit(self._run, fn, args))
+
+    def _abort(self):
+        for f in self._futures:
+            f.cancel()
+        self._pool.shutdown(wait=True)
+
+    def close(self) -> list:
+        """wait for every job; the results in submission order, or the first exception in that order"""
+        try:
+            return [f.result() for f in self._futures]
+        except BaseException:
+            self._abort()
+            raise
+        finally:
+            self._pool.shutdown(wait=True)
+
+
+def write_panel(path: str, panel: np.ndarray, fmt: str = "png") -> str:
+    """one panel [h, w, 3] uint8 to `path`: PNG through PIL at compress_level 1 (the writers are the slow side: a low
+    level keeps them near the device's pace), or .npy"""
+    if fmt == "png":
+        from PIL import Image
+        Image.fromarray(panel, "RGB").save(path, format="PNG", compress_level=1)
+    elif fmt == "npy":
+        np.save(path, panel)
+    else:
+        raise ValueError(f"write_panel: format must be 'png' or 'npy', got {fmt!r}")
+    return path
+
+
+def select_frames(psnr: np.ndarray, every: int = 1, top: Optional[int] = None) -> List[int]:
+    """which frames of a sub-video get a picture: of the predicted frames RGB_LEN_CLIP - 1 .. T - 1 every `every`-th,
+    and of those - with `top` - the `top` with the lowest `psnr` (the per-frame record; equal values: the earlier
+    frame first).  Ascending frame indices."""
+    if every < 1 or (top is not None and top < 1):
+        raise ValueError(f"select_frames: every >= 1 and top >= 1, got {every} and {top}")
+    frames = np.arange(RGB_LEN_CLIP - 1, len(psnr), every)
+    if top is not None and top < len(frames):
+        frames = frames[np.argsort(np.asarray(psnr)[frames], kind="stable")[:top]]
+    return sorted(int(f) for f in frames)
+
+
+def evaluate_dataset_panels(model, videos, dataset_name: str = "synthetic", panels_dir: Optional[str] = None, fmt: str = "png",
+                            every: int = 1, top: Optional[int] = None, workers: int = 8, device=None,
+                            stats: Optional[dict] = None, **render) -> dict:
+    """`evaluate_dataset_localised` (patch 16, no maps: its records are returned as they are) with pictures: every
+    sub-video is scored with `localise_subvideo`, `select_frames` picks its frames from the rgb PSNR record, and
+    `render_subvideo` re-runs the batches that hold one (`render`: its options).  `panels_dir`: the pictures go to
+    `panels_dir/NNNN/FFFFFF.<fmt>` (sub-video, frame) through an `OrderedWriterPool` of `workers` threads; None renders
+    and drops them (a warm-up).  Returns the record dict plus `panel_files` (in sub-video and frame order) and
+    `panel_frames` (per sub-video, the frames chosen).  `stats` receives `render_subvideo`'s counters, `write_s` (the
+    writers' busy seconds, summed over the threads) and `write_wait_s` (the seconds this thread waited for them)."""
+    import time
+    if fmt not in ("png", "npy"):
+        raise ValueError(f"evaluate_dataset_panels: format must be 'png' or 'npy', got {fmt!r}")
+    if device is None:
+        device = next(model.parameters()).device
+    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
+           "op_fea_comm_records": [], "rgb_patch_psnr_records": [], "n_frames": [], "panel_frames": [], "panel_files": []}
+    pool = OrderedWriterPool(workers) if panels_dir else None
+    counters: dict = {}
+    waited = 0.0
+    try:
+        for v, (rgb, op) in enumerate(videos):
+            rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+            rec = localise_subvideo(model, rgb, op)
+            out["rgb_img_pred_records"].append(rec["rgb_psnr"])
+            out["rgb_fea_comm_records"].append(rec["rgb_comm"])
+            out["op_img_pred_records"].append(rec["op_psnr"])
+            out["op_fea_comm_records"].append(rec["op_comm"])
+            with np.errstate(divide="ignore"):
+                out["rgb_patch_psnr_records"].append((10.0 * np.log10(1.0 / rec["rgb_worst"].astype(np.float64))).astype(np.float32))
+            out["n_frames"].append(int(rgb.shape[0]))
+            frames = select_frames(rec["rgb_psnr"], every, top)
+            out["panel_frames"].append(frames)
+            if panels_dir:
+                os.makedirs(os.path.join(panels_dir, f"{v:04d}"), exist_ok=True)
+            for f, panel in render_subvideo(model, rgb, op, select=frames, stats=counters, **render):
+                if pool is not None:
+                    t0 = time.perf_counter()
+                    pool.submit(write_panel, os.path.join(panels_dir, f"{v:04d}", f"{f:06d}.{fmt}"), panel, fmt)
+                    waited += time.perf_counter() - t0
+    except BaseException:
+        if pool is not None:
+            pool._abort()
+        raise
+    if pool is not None:
+        t0 = time.perf_counter()
+        out["panel_files"] = pool.close()
+        waited += time.perf_counter() - t0
+    if stats is not None:
+        stats.update(counters)
+        stats.update(write_s=pool.busy_s if pool is not None else 0.0, write_wait_s=waited)
+    return out
+
+
 def weights_init_normal(model: torch.nn.Module) -> None:
     """the reference's training-from-scratch init (utils/utils.py:328-334): Conv* ~ N(0, 0.02),
     BatchNorm2d gamma ~ N(1, 0.02), beta = 0; applied by class name exactly as there"""

@@ -415,6 +415,182 @@ def pixel_scores(map: torch.Tensor, mask: torch.Tensor, frac=(2, 5), out: dict |
     return res
 
 
+# ---- qualitative evaluation: panels of frames, colour-coded flows and error heat maps (csrc/render.hip) ----------
+
+RENDER_MAX_BATCH = 65535
+RENDER_MAX_PIXELS = 1 << 28  # h * w of one sample
+
+
+def _render_input(what: str, name: str, t, c: int, like=None) -> int:
+    """checks one fp32 [B, c, H, W] input of the render ops (a sample contiguous, any batch stride >= its size);
+    returns the batch stride in floats"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != c or t.dtype != torch.float32:
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be an fp32 [B, {c}, H, W] tensor, got {got}")
+    B, _, H, W = t.shape
+    if B < 1 or H < 1 or W < 1 or B > RENDER_MAX_BATCH or H * W > RENDER_MAX_PIXELS:
+        raise ValueError(f"{what}: 1 <= B <= {RENDER_MAX_BATCH}, H, W >= 1 and H * W <= {RENDER_MAX_PIXELS}, got {name} {tuple(t.shape)}")
+    if like is not None and (t.shape[0] != like.shape[0] or t.shape[2:] != like.shape[2:] or t.device != like.device):
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} on {t.device} does not match the batch, frame size and device of "
+                         f"{tuple(like.shape)} on {like.device}")
+    if not t[0].is_contiguous() or (B > 1 and t.stride(0) < c * H * W):
+        raise ValueError(f"{what}: {name}: a sample must be contiguous, with a batch stride >= C * H * W")
+    return max(t.stride(0), c * H * W) if B == 1 else t.stride(0)
+
+
+def _render_vector(what: str, name: str, v, B: int, dev) -> torch.Tensor:
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (B,) or v.device != dev or not v.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor [{B}] on {dev}")
+    return v
+
+
+def _render_scale(what: str, scale):
+    try:
+        su, sv = (float(s) for s in scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the flow scale must be a pair (su, sv), got {scale!r}") from None
+    if not (abs(su) < float("inf") and abs(sv) < float("inf")):
+        raise ValueError(f"{what}: the flow scale must be finite, got {scale!r}")
+    return su, sv
+
+
+def _render_out(what: str, out, shape, dev) -> tuple:
+    """the uint8 [B, h, w, 3] output (allocated when None) and its batch stride in bytes"""
+    B = shape[0]
+    per = shape[1] * shape[2] * 3
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != dev:
+        raise ValueError(f"{what}: out must be torch.uint8 {tuple(shape)} on {dev}")
+    elif not out[0].is_contiguous() or (B > 1 and out.stride(0) < per):
+        raise ValueError(f"{what}: out: a sample's picture must be contiguous, with a batch stride >= its size")
+    return out, (max(out.stride(0), per) if B == 1 else out.stride(0))
+
+
+def flow_to_rgb(flow: torch.Tensor, scale=(1.0, 1.0), max_rad: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The Middlebury colour code of a flow batch (csrc/render.hip; the definition is in include/ammc_hip.h): `flow` fp32
+    [B, 2, H, W] on the GPU, a sample contiguous, any batch stride (nothing is copied) -> uint8 [B, H, W, 3].  `scale` =
+    (su, sv) multiplies the two components first.  A pixel with a component beyond 1e7 or a NaN is unknown: black, and
+    outside the maximum.  `max_rad` fp32 [B]: the radius that maps to full saturation, per sample (pixels beyond it are
+    dimmed by a quarter); default each sample's own largest radius, taken by a launch of its own on the same stream.
+    The reference's `flow_to_image` but for the pixels that attain the maximum, which are always inside here.  `out`:
+    uint8 [B, H, W, 3] to write into, a sample's picture contiguous, any batch stride."""
+    what = "flow_to_rgb"
+    bs = _render_input(what, "flow", flow, 2)
+    su, sv = _render_scale(what, scale)
+    B, _, H, W = flow.shape
+    dev = flow.device
+    if max_rad is not None:
+        _render_vector(what, "max_rad", max_rad, B, dev)
+    out, out_bs = _render_out(what, out, (B, H, W, 3), dev)
+    _render_need_gpu(what, flow)
+    lib = _lib.load()
+    ws = torch.empty((B, 4), device=dev, dtype=torch.float32) if max_rad is None else None
+    _lib.check(lib.ammc_flow_colour_u8(_ptr(flow), bs, B, H, W, su, sv, _ptr(max_rad) if max_rad is not None else None,
+                                       _ptr(ws) if ws is not None else None, out.data_ptr(), out_bs, _stream(flow)), what)
+    return out
+
+
+def _render_inputs(what: str, rgb_pred, rgb_target, op_pred, op_target):
+    strides = [_render_input(what, "rgb_pred", rgb_pred, 3)]
+    strides.append(_render_input(what, "rgb_target", rgb_target, 3, rgb_pred))
+    strides.append(_render_input(what, "op_pred", op_pred, 2, rgb_pred))
+    strides.append(_render_input(what, "op_target", op_target, 2, rgb_pred))
+    return strides
+
+
+def _render_need_gpu(what: str, t: torch.Tensor):
+    if not t.is_cuda:
+        raise ValueError(f"{what}: the tensors must be on one GPU; there is no CPU fallback")
+
+
+def render_stats(rgb_pred: torch.Tensor, rgb_target: torch.Tensor, op_pred: torch.Tensor, op_target: torch.Tensor,
+                 flow_scale=(1.0, 1.0), out: torch.Tensor | None = None) -> torch.Tensor:
+    """The maxima the tiles of `render_panels` are normalised by, fp32 [B, 4]: the largest flow radius of the target and
+    of the predicted flow (components scaled by `flow_scale`, unknown pixels left out), the largest per-pixel error of
+    the frame pair and of the flow pair (`error_maps`' `pixel`; a NaN and an unknown flow pixel count as 0).  One launch
+    behind a memset of `out` on torch's current stream; exact maxima: the same bits on every launch."""
+    what = "render_stats"
+    strides = _render_inputs(what, rgb_pred, rgb_target, op_pred, op_target)
+    su, sv = _render_scale(what, flow_scale)
+    B, _, H, W = rgb_pred.shape
+    dev = rgb_pred.device
+    if out is None:
+        out = torch.empty((B, 4), device=dev, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, 4) or out.device != dev \
+            or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be contiguous torch.float32 {(B, 4)} on {dev}")
+    _render_need_gpu(what, rgb_pred)
+    lib = _lib.load()
+    _lib.check(lib.ammc_render_stats_f32(_ptr(rgb_pred), strides[0], _ptr(rgb_target), strides[1], _ptr(op_pred), strides[2],
+                                         _ptr(op_target), strides[3], B, H, W, su, sv, _ptr(out), _stream(rgb_pred)), what)
+    return out
+
+
+def render_panels(rgb_pred: torch.Tensor, rgb_target: torch.Tensor, op_pred: torch.Tensor, op_target: torch.Tensor,
+                  tiles=None, flow_scale=(1.0, 1.0), flow_norm="target", heat_max="frame", alpha: float = 0.6,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Pictures of a batch of predictions (csrc/render.hip; definitions in include/ammc_hip.h): `rgb_pred`, `rgb_target`
+    fp32 [B, 3, H, W] on the model's [-1, 1] range, `op_pred`, `op_target` fp32 [B, 2, H, W], on one GPU, a sample
+    contiguous, any batch strides (nothing is copied) -> uint8 [B, rows * H, cols * W, 3]: per sample a panel of tiles.
+    `tiles`: a row of names or rows of equal length, an ordered subset of `harness.RENDER_TILES` - `rgb_target`,
+    `rgb_pred` (the frames), `rgb_heat` (the per-pixel error of the frame pair as a heat map over the grey target),
+    `op_target`, `op_pred` (the Middlebury colour code, components scaled by `flow_scale` first), `op_heat`; default
+    all six, 2 x 3.  `flow_norm`: "target" colours both flows by the target's largest radius (the two tiles are
+    comparable), "each" every flow by its own (the reference's per-image behaviour), a tensor [B] by the given radius.
+    `heat_max`: "frame" scales a heat tile by its sample's largest error, a tensor [B] (both streams) or a pair of them
+    (frame pair, flow pair) by fixed values: pictures of different frames are then comparable.  `alpha`: the weight of
+    the heat colour over the grey.  Two launches on torch's current stream (one where every normalisation is given).
+    `out`: uint8 [B, rows * H, cols * W, 3] to write into, a sample's panel contiguous, any batch stride."""
+    from .harness import RENDER_DEFAULT_TILES, RENDER_TILES, panel_layout
+    what = "render_panels"
+    strides = _render_inputs(what, rgb_pred, rgb_target, op_pred, op_target)
+    su, sv = _render_scale(what, flow_scale)
+    rows = panel_layout(RENDER_DEFAULT_TILES if tiles is None else tiles)
+    ids = [RENDER_TILES.index(t) for row in rows for t in row]
+    try:
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: alpha must be a number in [0, 1], got {alpha!r}") from None
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{what}: alpha must be a number in [0, 1], got {alpha!r}")
+    B, _, H, W = rgb_pred.shape
+    dev = rgb_pred.device
+    max_rad, each = None, 0
+    if isinstance(flow_norm, str):
+        if flow_norm not in ("target", "each"):
+            raise ValueError(f"{what}: flow_norm must be 'target', 'each' or a tensor [B], got {flow_norm!r}")
+        each = int(flow_norm == "each")
+    else:
+        max_rad = _render_vector(what, "flow_norm", flow_norm, B, dev)
+    heat_rgb = heat_op = None
+    if isinstance(heat_max, str):
+        if heat_max != "frame":
+            raise ValueError(f"{what}: heat_max must be 'frame', a tensor [B] or a pair of them, got {heat_max!r}")
+    elif isinstance(heat_max, (tuple, list)):
+        if len(heat_max) != 2:
+            raise ValueError(f"{what}: heat_max must be 'frame', a tensor [B] or a pair of them, got {len(heat_max)} values")
+        heat_rgb = _render_vector(what, "heat_max[0]", heat_max[0], B, dev)
+        heat_op = _render_vector(what, "heat_max[1]", heat_max[1], B, dev)
+    else:
+        heat_rgb = heat_op = _render_vector(what, "heat_max", heat_max, B, dev)
+    out, out_bs = _render_out(what, out, (B, len(rows) * H, len(rows[0]) * W, 3), dev)
+    _render_need_gpu(what, rgb_pred)
+    lib = _lib.load()
+    import ctypes
+    need = (max_rad is None and (3 in ids or 4 in ids)) or (heat_rgb is None and 2 in ids) or (heat_op is None and 5 in ids)
+    stream = _stream(rgb_pred)
+    ptrs = [_ptr(rgb_pred), strides[0], _ptr(rgb_target), strides[1], _ptr(op_pred), strides[2], _ptr(op_target), strides[3]]
+    stats = None
+    if need:
+        stats = torch.empty((B, 4), device=dev, dtype=torch.float32)
+        _lib.check(lib.ammc_render_stats_f32(*ptrs, B, H, W, su, sv, _ptr(stats), stream), "render_panels (stats)")
+    opt = [_ptr(t) if t is not None else None for t in (stats, max_rad, heat_rgb, heat_op)]
+    _lib.check(lib.ammc_render_panels_u8(*ptrs, B, H, W, su, sv, (ctypes.c_int32 * len(ids))(*ids), len(rows), len(rows[0]),
+                                         opt[0], each, opt[1], opt[2], opt[3], alpha, out.data_ptr(), out_bs, stream), what)
+    return out
+
+
 def _nhwc_strides(t: torch.Tensor):
     """(batch, row, pixel) strides of an NHWC view [B, h, w, C] for `ammc_memory_scores_f32`; a dimension of size 1 may
     carry any stride in torch - it is given the extent below it instead"""

@@ -870,6 +870,63 @@ int ammc_pixel_scores_f32(const float* map, int64_t map_bs, const uint8_t* mask,
                           int32_t w, int32_t frac_num, int32_t frac_den, int32_t* m, float* kth, float* max_in,
                           float* max_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Qualitative evaluation (csrc/render.hip): finished uint8 panels of the predicted and target frames, the Middlebury
+ * colour code of the predicted and target flows and heat maps of their per-pixel errors, from a pass of its own.
+ *   rgb_pred, rgb_target   fp32 [batch][3][h][w] on the model's [-1, 1] range
+ *   op_pred, op_target     fp32 [batch][2][h][w] flows
+ * DEVICE arrays, a sample contiguous, each with a batch stride of its own in floats (>= the sample's size).
+ * All arithmetic is fp32; no product is contracted into a sum except where an fma is named.
+ * Frame tile.  Per channel u8 = floor(clamp((x + 1) * 127.5, 0, 255) + 0.5), taken of the real value: x is clamped to
+ *   [-1, 1] (a NaN to -1), y = fma(x, 127.5, 128), n = floor(y), and n steps back by one where fma(x, 127.5, 128 - n) < 0.
+ * Flow tile.  The Middlebury colour code.  wheel[1..55][3]: the colour wheel of the segment lengths 15, 6, 4, 11, 13, 6
+ *   (red-yellow, yellow-green, green-cyan, cyan-blue, blue-magenta, magenta-red; along a segment of length n one channel
+ *   holds 255 and one ramps floor(255 i / n), up in the 1st, 3rd and 5th segment and down from 255 in the others), each
+ *   value divided by 255.  u = su * flow[0], v = sv * flow[1].  A pixel with |u| > 1e7, |v| > 1e7 or a NaN is UNKNOWN: it
+ *   is drawn black and enters no maximum (as u = v = 0).  raw = sqrt(u * u + v * v); maxrad: the sample's largest raw,
+ *   or a supplied value; inv = 1 / (maxrad + 2^-52); a = atan2(-v, -u) / pi; fk = (a + 1) / 2 * 54 + 1; k0 = floor(fk)
+ *   (kept in 1..55); k1 = k0 + 1, 56 wrapping to 1; f = fk - k0; per channel col = (1 - f) * wheel[k0] + f * wheel[k1];
+ *   a pixel is INSIDE when raw <= maxrad, then col = 1 - rad * (1 - col) with rad = min(raw * inv, 1); otherwise
+ *   col = col * 0.75; u8 = floor(255 * col).  A zero flow is white.
+ * Heat tile.  e = ((d_0^2 + d_1^2) + ...) / c with d_ch = 0.5 * (target_ch - pred_ch): ammc_error_maps_f32's `pixel`.
+ *   A NaN e counts as 0, and so does the flow pair's e where either flow is unknown.  t = min(e / heat_max, 1), 0 where
+ *   heat_max <= 0, with heat_max the sample's largest e or a supplied value; colour (r, g, b) = clamp(1.5 - |4 t - 3|,
+ *   0, 1), clamp(1.5 - |4 t - 2|, 0, 1), clamp(1.5 - |4 t - 1|, 0, 1); u8 = floor(((1 - alpha) * grey + (alpha * 255) *
+ *   colour) + 0.5) with grey = (r + g + b) / 3 of the target's frame tile bytes, 128 for the flow pair.
+ *
+ * ammc_render_stats_f32: stats[b] = (largest raw of op_target, largest raw of op_pred, largest e of the frame pair,
+ *   largest e of the flow pair), fp32 [batch][4].  An input may be NULL (the frame pair: both or neither; not all
+ *   four): the values that would read it are 0.  A memset node that zeroes stats and one kernel launch on `stream`; the
+ *   workgroups publish their maxima by integer atomic maxima of the floats' bits (non-negative, never NaN: the order of
+ *   the bits is the order of the values), so stats holds THE maxima: the same bits on every launch and for every launch
+ *   geometry, whatever stats held before, equal to an IEEE fp32 restatement (square root correctly rounded).
+ * ammc_render_panels_u8: out[b] = uint8 [rows * h][cols * w][3], samples out_bs BYTES apart: tile tiles[r * cols + c]
+ *   at rows [r h, (r + 1) h) and columns [c w, (c + 1) w).  tiles: a HOST array of rows * cols <= 6 tile ids, read
+ *   during the call, each id at most once: 0 rgb_target, 1 rgb_pred, 2 rgb_heat, 3 op_target, 4 op_pred, 5 op_heat.
+ *   An input no chosen tile reads may be NULL.  Normalisation: max_rad [batch] (both flow tiles), heat_rgb [batch],
+ *   heat_op [batch] where given, otherwise stats [batch][4] as ammc_render_stats_f32 left them on the same stream:
+ *   op_target by stats[b][0]; op_pred by stats[b][0] too (flow_each = 0: the two tiles are comparable) or by its own
+ *   stats[b][1] (flow_each = 1).  stats may be NULL where nothing reads it.  One launch; plain stores, every byte
+ *   written once; a sample's panel is a function of the sample and the arguments alone.  16-byte loads and dword stores
+ *   where w % 4 == 0 and the bases and batch strides allow, scalar loads and byte stores otherwise: the same bytes.
+ * ammc_flow_colour_u8: the colour code of a flow batch alone, out[b] = uint8 [h][w][3]; max_rad [batch] or NULL: by the
+ *   sample's own maximum, taken into workspace (4 * batch floats, zeroed inside the call) by the stats launch.
+ * AMMC_EINVAL: a missing pointer; batch, h or w < 1; su or sv not finite; alpha outside [0, 1]; flow_each not 0 / 1;
+ *   rows or cols < 1, rows * cols > 6, a tile id outside 0..5 or given twice; a float pointer not 4-byte aligned; with
+ *   batch > 1 a batch stride smaller than a sample.  AMMC_EUNSUP: batch > 65535; h * w > 2^28.
+ * All of them are decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_render_stats_f32(const float* rgb_pred, int64_t rp_bs, const float* rgb_target, int64_t rt_bs, const float* op_pred,
+                          int64_t fp_bs, const float* op_target, int64_t ft_bs, int32_t batch, int32_t h, int32_t w, float su,
+                          float sv, float* stats, void* stream);
+int ammc_render_panels_u8(const float* rgb_pred, int64_t rp_bs, const float* rgb_target, int64_t rt_bs, const float* op_pred,
+                          int64_t fp_bs, const float* op_target, int64_t ft_bs, int32_t batch, int32_t h, int32_t w, float su,
+                          float sv, const int32_t* tiles, int32_t rows, int32_t cols, const float* stats, int32_t flow_each,
+                          const float* max_rad, const float* heat_rgb, const float* heat_op, float alpha, uint8_t* out,
+                          int64_t out_bs, void* stream);
+int ammc_flow_colour_u8(const float* flow, int64_t flow_bs, int32_t batch, int32_t h, int32_t w, float su, float sv,
+                        const float* max_rad, float* workspace, uint8_t* out, int64_t out_bs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
