@@ -50,6 +50,7 @@ extern "C" int ammc_frames_u8_to_f32(const uint8_t* src, int32_t n, int32_t h, i
                                      int32_t ow, int32_t bgr, void* stream) {
   if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return AMMC_EINVAL;
   const int64_t total = (int64_t)n * oh * ow;
+  if ((total + 255) / 256 > 0x7fffffff) return AMMC_EINVAL;
   hipLaunchKernelGGL(frames_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, n,
                      h, w, dst, oh, ow, bgr ? 1 : 0, (double)w / (double)ow, (double)h / (double)oh);
   return ammc_launch_status();
@@ -59,6 +60,7 @@ extern "C" int ammc_flows_to_f32(const float* src, int32_t n, int32_t h, int32_t
                                  void* stream) {
   if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) return AMMC_EINVAL;
   const int64_t total = (int64_t)n * oh * ow;
+  if ((total + 255) / 256 > 0x7fffffff) return AMMC_EINVAL;
   hipLaunchKernelGGL(flows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, n, h,
                      w, dst, oh, ow, (double)w / (double)ow, (double)h / (double)oh);
   return ammc_launch_status();

@@ -74,6 +74,37 @@ def test_bank_gather_is_bit_identical_to_the_loaders(tmp_path, h, w, oh, ow):
             assert torch.equal(g_op[s], ev_op[s:s + 4])
 
 
+def test_sub_videos_of_different_source_sizes_share_one_bank(tmp_path):
+    """`_fill` resizes every sub-video from its own source size: 12 x 16 and 9 x 21 into one 8 x 8 bank, each gathered
+    clip bit-identical to the loaders on its own frames"""
+    rng = np.random.default_rng(53)
+    vids = []
+    for v, (h, w) in enumerate(((12, 16), (9, 21))):
+        dr, do = tmp_path / "rgb" / f"{v + 1:02d}", tmp_path / "op" / f"{v + 1:02d}"
+        dr.mkdir(parents=True)
+        do.mkdir(parents=True)
+        fr = rng.integers(0, 256, (RGB_LENS[v], h, w, 3), dtype=np.uint8)
+        fl = rng.normal(0, 3, (OP_LENS[v], h, w, 2)).astype(np.float32)
+        for i in range(RGB_LENS[v]):
+            np.save(dr / f"{i:04d}.npy", fr[i])
+        for i in range(OP_LENS[v]):
+            PO.write_flo(str(do / f"{i:04d}.flo"), fl[i])
+        vids.append((fr, fl))
+    bank = P.ClipBank(str(tmp_path / "rgb"), str(tmp_path / "op"), 8, DEV, workers=2, budget_gb=4.0)
+    assert tuple(bank.rgb.shape) == (sum(RGB_LENS), 3, 8, 8) and tuple(bank.op.shape) == (sum(OP_LENS), 8, 8)
+    # every clip either video holds
+    pairs = [(v, s, min(s, OP_LENS[v] - 4)) for v in range(2) for s in range(RGB_LENS[v] - 4)]
+    rv, rs, os_ = np.array(pairs).T
+    rf, of = bank.global_index(rv, rs, rv, os_)
+    rgb, op = bank.gather(rf, of)
+    torch.cuda.synchronize()
+    rgb, op = rgb.cpu().numpy(), op.cpu().numpy()
+    for i, (v, s, so) in enumerate(pairs):
+        fr, fl = vids[v]
+        assert np.array_equal(rgb[i], np.stack([PO.load_frame(fr[s + t], (8, 8)) for t in range(5)])), (v, s)
+        assert np.array_equal(op[i], np.stack([PO.load_op(fl[so + t].copy(), (8, 8)) for t in range(4)])), (v, so)
+
+
 def test_gather_refuses_bad_indices_before_the_launch(tmp_path):
     _tree(tmp_path, 12, 16, 3, png=False)
     bank = P.ClipBank(str(tmp_path / "rgb"), str(tmp_path / "op"), 16, DEV, workers=2)
