@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import contextlib
 import os
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -291,80 +291,88 @@ def assemble_localised(n_frames: int, batches, parts: Sequence[Dict[str, np.ndar
     return rec
 
 
-class _Slots:
-    """one flat fp32 device buffer per sub-video, carved into the per-clip outputs of both streams (a batch writes
-    straight into its clips' rows through `ops.error_maps(out=...)`) and the per-batch commit values and range flags: the
-    whole sub-video comes to the host by ONE copy"""
+# ---- the pass driver: one sub-video through a pass behind the evaluation forward -------------
 
-    def __init__(self, n_clip: int, n_batch: int, shapes, patch: int, pixel: bool, device):
-        self.layout, off = {}, 0
+class _FlatSlots:
+    """one flat 4-byte device buffer per sub-video carved into named sections (fp32, or int32 for the names in
+    `ints`): batches write straight into their clips' rows and the whole sub-video comes to the host by ONE copy"""
 
-        def carve(name, shape):
-            nonlocal off
-            n = int(np.prod(shape))
-            self.layout[name] = (off, shape)
-            off += (n + 3) // 4 * 4                                         # sections start 16-byte aligned
-        for st, (_, h, w) in zip(("rgb", "op"), shapes):
-            ph, pw = (h + patch - 1) // patch, (w + patch - 1) // patch
-            carve(f"{st}_patch", (n_clip, ph, pw))
-            carve(f"{st}_patch_sum", (n_clip, ph, pw))
-            for k in ("frame_sq", "psnr", "worst", "worst_idx"):
-                carve(f"{st}_{k}", (n_clip,))
-            if pixel:
-                carve(f"{st}_pixel", (n_clip, h, w))
-        carve("comm", (n_batch, 2))
-        carve("flag", (n_batch,))
+    def __init__(self, sections, ints, device):
+        self.layout, self.ints, off = {}, set(ints), 0
+        for name, shape in sections:
+            self.layout[name] = (off, tuple(shape))
+            off += (int(np.prod(shape)) + 3) // 4 * 4                          # sections start 16-byte aligned
         self.flat = torch.zeros(off, device=device, dtype=torch.float32)
 
     def view(self, name: str, flat=None):
         off, shape = self.layout[name]
         v = (self.flat if flat is None else flat)[off:off + int(np.prod(shape))]
-        if name.endswith("_worst_idx"):
+        if name in self.ints:
             v = v.view(torch.int32) if isinstance(v, torch.Tensor) else v.view(np.int32)
         return v.reshape(shape)
 
 
-def localise_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, patch: int = 16, pixel: bool = False,
-                      batch: int = EVAL_BATCH, predictions: Optional[list] = None) -> Dict[str, np.ndarray]:
-    """Where the anomaly is: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and on the model's device ->
-    per-frame numpy arrays of the sub-video: `rgb_patch` / `op_patch` [T,ph,pw] (patch means of the squared [0,1]-range
-    error), `rgb_psnr` / `op_psnr` (from the fixed-order sum: the same bits for the same predictions), `rgb_worst` /
-    `op_worst` (the largest patch mean), `rgb_worst_idx` / `op_worst_idx` (its i * pw + j), `rgb_comm` / `op_comm` [T],
-    and with `pixel` `rgb_pixel` / `op_pixel` [T,H,W].  Clips, targets and batches are those of `score_batch_device`
-    (`batch` clips at a time), the forward is the model's evaluation forward, frame indexing and fills are
-    `assemble_records`' (`assemble_localised`).  Every batch is queued back to back; one device-to-host copy per
-    sub-video; a batch whose S16 range flag is set is re-run with `exact=True`, as `score_batch` does.
-    `predictions`: a testing and cross-check hook, not part of the scoring - an optional list that receives
-    (s, e, rgb_pred, op_pred, fused) of every batch as scored (it keeps every batch's predicted frames alive); `fused` = the
-    [rgb, op] PSNR of the output layer's epilogue from the same forward."""
-    from . import ops
+def _checked_batches(who: Optional[str], rgb_frames: torch.Tensor, op_frames: torch.Tensor, batch: int):
+    """the checks every per-sub-video pass makes, then `subvideo_batches(T, batch)`.  `who`: the public function's name
+    for the residency message; None leaves that check out (the driver itself runs on tensors of any device)"""
     t = rgb_frames.shape[0]
     if op_frames.shape[0] != t - 1:
         raise ValueError("a sub-video of T frames has T-1 flows")
-    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
-        raise ValueError("localise_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
+    if who is not None and not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous()
+                                and op_frames.is_contiguous()):
+        raise ValueError(f"{who} reads a sub-video resident on the GPU (contiguous tensors): move it there first")
     batches = subvideo_batches(t, batch)
     if not batches:
         raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
+    return batches
+
+
+class _Forward(NamedTuple):
+    """what `_forward_batch` hands to a pass: the predicted frames and flows, the memory blocks' two commit values, the
+    [rgb, op] PSNR of the output layer's epilogue, the (rgb, op) targets and the S16 range flag ([1] tensor, or None)"""
+    rgb_pred: torch.Tensor
+    op_pred: torch.Tensor
+    diffs: tuple
+    fused: list
+    targets: tuple
+    overflow: Optional[torch.Tensor]
+
+
+def _forward_batch(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, s: int, e: int, exact: bool) -> _Forward:
+    """clips [s, e) of a resident sub-video through the model's evaluation forward: the clips are overlapping windows
+    (`clip_windows`), the targets plain slices, the range guard is deferred (nothing waits for the device)"""
+    rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
+    op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
+    targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+    with torch.no_grad():
+        (rgb_out, op_out, diffs, _), *fused = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
+    return _Forward(rgb_out, op_out, diffs, fused, targets, getattr(model, "last_overflow", None))
+
+
+def _run_pass(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, batches, sections, ints, on_batch: Callable,
+              predictions: Optional[list] = None, scratch=()) -> Dict[str, np.ndarray]:
+    """One sub-video through a pass; the tensors may live on any device.  `sections`: [(name, shape of one clip's row)],
+    every name with the prefix of its stream (`rgb_` / `op_`: it picks the clip length of the fills); `ints`: the names
+    that hold int32; `scratch`: names a kernel needs room for but the pass does not return.  The driver carves the
+    sections, and behind them the per-batch commit values and range flags, out of one `_FlatSlots` buffer.  For batch k
+    = clips [s, e) it runs `_forward_batch`, then `on_batch(slots, s, e, k, forward)` under `no_grad`, which writes the
+    pass's outputs into rows [s, e) of its sections (device work only: no wait, no host read).  Every batch is queued
+    back to back; ONE device-to-host copy; the batches whose S16 range flag came back set run again with `exact=True`
+    (one `_count_fallback` each) and the buffer is copied again.  `predictions` receives (s, e, rgb_pred, op_pred, fused)
+    of every batch as scored: a re-run's tuple replaces the plain one.  -> `assemble_localised` over the sections that
+    are not scratch, plus `rgb_comm` / `op_comm`."""
     n_clip = batches[-1][1]
-    slots = _Slots(n_clip, len(batches), (rgb_frames.shape[1:], op_frames.shape[1:]), patch, pixel, rgb_frames.device)
+    slots = _FlatSlots([(name, (n_clip,) + tuple(shape)) for name, shape in sections] +
+                       [("comm", (len(batches), 2)), ("flag", (len(batches),))], ints, rgb_frames.device)
 
     def run(k: int, exact: bool):
         s, e = batches[k]
-        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
-        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
-        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        fwd = _forward_batch(model, rgb_frames, op_frames, s, e, exact)
         with torch.no_grad():
-            (rgb_out, op_out, diffs, _), *fused = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
-            flag = getattr(model, "last_overflow", None)
-            for st, pred, tgt in (("rgb", rgb_out, targets[0]), ("op", op_out, targets[1])):
-                out = {"patch_mean": slots.view(f"{st}_patch")[s:e], "patch_sum": slots.view(f"{st}_patch_sum")[s:e]}
-                for key in ("frame_sq", "worst", "worst_idx") + (("pixel",) if pixel else ()):
-                    out[key] = slots.view(f"{st}_{key}")[s:e]
-                slots.view(f"{st}_psnr")[s:e] = ops.error_maps(pred, tgt, patch, pixel, out)["psnr"]
-            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
-            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
-        return (s, e, rgb_out, op_out, fused) if predictions is not None else None      # (else the frames are let go)
+            on_batch(slots, s, e, k, fwd)
+            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = fwd.diffs[0].reshape(()), fwd.diffs[1].reshape(())
+            slots.view("flag")[k] = fwd.overflow.reshape(()).to(torch.float32) if fwd.overflow is not None else 0.0
+        return (s, e, fwd.rgb_pred, fwd.op_pred, fwd.fused) if predictions is not None else None    # (else the frames are let go)
 
     done = [run(k, False) for k in range(len(batches))]
     host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
@@ -376,15 +384,85 @@ def localise_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, 
         host = slots.flat.cpu().numpy()
     if predictions is not None:
         predictions.extend(done)
+    names = [name for name, _ in sections if name not in scratch]
     parts = []
     for k, (s, e) in enumerate(batches):
-        part = {}
-        for st in ("rgb", "op"):
-            for key in ("patch", "psnr", "worst", "worst_idx") + (("pixel",) if pixel else ()):
-                part[f"{st}_{key}"] = slots.view(f"{st}_{key}", host)[s:e]
+        part = {name: slots.view(name, host)[s:e] for name in names}
         part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
         parts.append(part)
-    return assemble_localised(t, batches, parts)
+    return assemble_localised(rgb_frames.shape[0], batches, parts)
+
+
+def _new_records(dataset_name: str, *more: str) -> dict:
+    """the record dict of an `evaluate_dataset_*` loop: the reference's four lists, then the loop's own"""
+    return {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
+            "op_fea_comm_records": [], **{key: [] for key in more}}
+
+
+def _scored_subvideos(model, videos, out: dict, score: Callable, device=None):
+    """the loop of the `evaluate_dataset_*` functions: every (rgb, op) of `videos` is moved to `device` (default: the
+    model's) and made contiguous, `score(v, rgb, op)` returns its per-frame arrays, the four reference record lists and
+    `n_frames` of `out` grow by one entry; yields (v, rgb, op, rec) for the caller's own records"""
+    if device is None:
+        device = next(model.parameters()).device
+    for v, (rgb, op) in enumerate(videos):
+        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+        rec = score(v, rgb, op)
+        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
+        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
+        out["op_img_pred_records"].append(rec["op_psnr"])
+        out["op_fea_comm_records"].append(rec["op_comm"])
+        out["n_frames"].append(int(rgb.shape[0]))
+        yield v, rgb, op, rec
+
+
+def _write_maps(out: dict, maps_dir: Optional[str], v: int, rec: Dict[str, np.ndarray]) -> None:
+    """with `maps_dir`: sub-video v's arrays to `maps_dir/NNNN.npz`, the path to `out["map_files"]`"""
+    if maps_dir:
+        os.makedirs(maps_dir, exist_ok=True)
+        path = os.path.join(maps_dir, f"{v:04d}.npz")
+        np.savez(path, **rec)
+        out["map_files"].append(path)
+
+
+def _worst_patch_psnr(worst: np.ndarray) -> np.ndarray:
+    """10 log10(1 / worst patch mean) per frame, fp32 (inf where the worst patch has no error)"""
+    with np.errstate(divide="ignore"):
+        return (10.0 * np.log10(1.0 / worst.astype(np.float64))).astype(np.float32)
+
+
+def localise_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, patch: int = 16, pixel: bool = False,
+                      batch: int = EVAL_BATCH, predictions: Optional[list] = None) -> Dict[str, np.ndarray]:
+    """Where the anomaly is: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and on the model's device ->
+    per-frame numpy arrays of the sub-video: `rgb_patch` / `op_patch` [T,ph,pw] (patch means of the squared [0,1]-range
+    error), `rgb_psnr` / `op_psnr` (from the fixed-order sum: the same bits for the same predictions), `rgb_worst` /
+    `op_worst` (the largest patch mean), `rgb_worst_idx` / `op_worst_idx` (its i * pw + j), `rgb_comm` / `op_comm` [T],
+    and with `pixel` `rgb_pixel` / `op_pixel` [T,H,W].  Clips, targets and batches are those of `score_batch_device`
+    (`batch` clips at a time), the forward is the model's evaluation forward, frame indexing and fills are
+    `assemble_records`' (`assemble_localised`).  Every batch is queued back to back; one device-to-host copy per
+    sub-video; a batch whose S16 range flag is set is re-run with `exact=True`, as `score_batch` does (`_run_pass`).
+    `predictions`: a testing and cross-check hook, not part of the scoring - an optional list that receives
+    (s, e, rgb_pred, op_pred, fused) of every batch as scored (it keeps every batch's predicted frames alive); `fused` = the
+    [rgb, op] PSNR of the output layer's epilogue from the same forward."""
+    from . import ops
+    batches = _checked_batches("localise_subvideo", rgb_frames, op_frames, batch)
+    sections = []
+    for st, (_, h, w) in (("rgb", rgb_frames.shape[1:]), ("op", op_frames.shape[1:])):
+        grid = ((h + patch - 1) // patch, (w + patch - 1) // patch)
+        sections += [(f"{st}_patch", grid), (f"{st}_patch_sum", grid)]
+        sections += [(f"{st}_{key}", ()) for key in ("frame_sq", "psnr", "worst", "worst_idx")]
+        if pixel:
+            sections.append((f"{st}_pixel", (h, w)))
+
+    def on_batch(slots, s, e, k, fwd):
+        for st, pred, tgt in (("rgb", fwd.rgb_pred, fwd.targets[0]), ("op", fwd.op_pred, fwd.targets[1])):
+            out = {"patch_mean": slots.view(f"{st}_patch")[s:e], "patch_sum": slots.view(f"{st}_patch_sum")[s:e]}
+            for key in ("frame_sq", "worst", "worst_idx") + (("pixel",) if pixel else ()):
+                out[key] = slots.view(f"{st}_{key}")[s:e]
+            slots.view(f"{st}_psnr")[s:e] = ops.error_maps(pred, tgt, patch, pixel, out)["psnr"]
+
+    return _run_pass(model, rgb_frames, op_frames, batches, sections, ("rgb_worst_idx", "op_worst_idx"), on_batch, predictions,
+                     scratch=("rgb_patch_sum", "rgb_frame_sq", "op_patch_sum", "op_frame_sq"))
 
 
 def evaluate_dataset_localised(model, videos, dataset_name: str = "synthetic", patch: int = 16, pixel: bool = False,
@@ -395,26 +473,11 @@ def evaluate_dataset_localised(model, videos, dataset_name: str = "synthetic", p
     reference with `*_img_pred_records` from the fixed-order PSNR, plus `rgb_patch_psnr_records` (10 log10(1 / worst
     patch mean) per frame: the worst-patch frame score, a drop-in for `rgb_img_pred_records` in `fuse_scores_auc`) and
     `n_frames`.  `maps_dir`: one `NNNN.npz` per sub-video with the arrays of `localise_subvideo` (`map_files`)."""
-    if device is None:
-        device = next(model.parameters()).device
-    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
-           "op_fea_comm_records": [], "rgb_patch_psnr_records": [], "n_frames": [], "map_files": []}
-    if maps_dir:
-        os.makedirs(maps_dir, exist_ok=True)
-    for v, (rgb, op) in enumerate(videos):
-        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
-        rec = localise_subvideo(model, rgb, op, patch, pixel)
-        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
-        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
-        out["op_img_pred_records"].append(rec["op_psnr"])
-        out["op_fea_comm_records"].append(rec["op_comm"])
-        with np.errstate(divide="ignore"):
-            out["rgb_patch_psnr_records"].append((10.0 * np.log10(1.0 / rec["rgb_worst"].astype(np.float64))).astype(np.float32))
-        out["n_frames"].append(int(rgb.shape[0]))
-        if maps_dir:
-            path = os.path.join(maps_dir, f"{v:04d}.npz")
-            np.savez(path, **rec)
-            out["map_files"].append(path)
+    out = _new_records(dataset_name, "rgb_patch_psnr_records", "n_frames", "map_files")
+    for v, _, _, rec in _scored_subvideos(model, videos, out, lambda v, rgb, op: localise_subvideo(model, rgb, op, patch, pixel),
+                                          device):
+        out["rgb_patch_psnr_records"].append(_worst_patch_psnr(rec["rgb_worst"]))
+        _write_maps(out, maps_dir, v, rec)
     return out
 
 
@@ -455,25 +518,6 @@ def memory_scores_reference(enc_w: torch.Tensor, enc_b: torch.Tensor, embed: tor
             "scale": (znorm + (near * near).sum(-1)) / d}
 
 
-class _FlatSlots:
-    """one flat 4-byte device buffer per sub-video carved into named sections (fp32, or int32 for the names in
-    `ints`): batches write straight into their clips' rows and the whole sub-video comes to the host by ONE copy"""
-
-    def __init__(self, sections, ints, device):
-        self.layout, self.ints, off = {}, set(ints), 0
-        for name, shape in sections:
-            self.layout[name] = (off, tuple(shape))
-            off += (int(np.prod(shape)) + 3) // 4 * 4                          # sections start 16-byte aligned
-        self.flat = torch.zeros(off, device=device, dtype=torch.float32)
-
-    def view(self, name: str, flat=None):
-        off, shape = self.layout[name]
-        v = (self.flat if flat is None else flat)[off:off + int(np.prod(shape))]
-        if name in self.ints:
-            v = v.view(torch.int32) if isinstance(v, torch.Tensor) else v.view(np.int32)
-        return v.reshape(shape)
-
-
 def memory_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, batch: int = EVAL_BATCH,
                     indices: bool = False) -> Dict[str, np.ndarray]:
     """Which clips the memory does not hold: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W], contiguous and on the model's
@@ -486,63 +530,28 @@ def memory_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, ba
     (`model.bottleneck_inputs()`) with that stream's `vq_down3`.  One device-to-host copy per sub-video; a batch whose
     S16 range flag is set is re-run with `exact=True`, and its memory pass with it."""
     from . import ops
-    t = rgb_frames.shape[0]
-    if op_frames.shape[0] != t - 1:
-        raise ValueError("a sub-video of T frames has T-1 flows")
-    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
-        raise ValueError("memory_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
-    batches = subvideo_batches(t, batch)
-    if not batches:
-        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
-    n_clip = batches[-1][1]
+    batches = _checked_batches("memory_subvideo", rgb_frames, op_frames, batch)
     quans = {"rgb": model.rgb.vq_down3, "op": model.op.vq_down3}
-    ks = {st: int(getattr(q, "quan", q).quantize.k) for st, q in quans.items()}
     sections, ints = [], []
     for st, frames in (("rgb", rgb_frames), ("op", op_frames)):
-        h, w = frames.shape[2] // 8, frames.shape[3] // 8
-        sections += [(f"{st}_commit_map", (n_clip, h, w)), (f"{st}_clip_comm", (n_clip,)), (f"{st}_commit_worst", (n_clip,)),
-                     (f"{st}_commit_worst_idx", (n_clip,)), (f"{st}_psnr", (n_clip,))]
+        grid = (frames.shape[2] // 8, frames.shape[3] // 8)
+        sections += [(f"{st}_commit_map", grid), (f"{st}_clip_comm", ()), (f"{st}_commit_worst", ()),
+                     (f"{st}_commit_worst_idx", ()), (f"{st}_psnr", ())]
         ints.append(f"{st}_commit_worst_idx")
         if indices:
-            sections.append((f"{st}_slots", (n_clip, h, w, ks[st])))
+            sections.append((f"{st}_slots", grid + (int(getattr(quans[st], "quan", quans[st]).quantize.k),)))
             ints.append(f"{st}_slots")
-    sections += [("comm", (len(batches), 2)), ("flag", (len(batches),))]
-    slots = _FlatSlots(sections, ints, rgb_frames.device)
 
-    def run(k: int, exact: bool):
-        s, e = batches[k]
-        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
-        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
-        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
-        with torch.no_grad():
-            (_, _, diffs, _), *psnr = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
-            flag = getattr(model, "last_overflow", None)
-            for st, x4, ps in zip(("rgb", "op"), model.bottleneck_inputs(), psnr):
-                out = {"map": slots.view(f"{st}_commit_map")[s:e], "commit": slots.view(f"{st}_clip_comm")[s:e],
-                       "worst": slots.view(f"{st}_commit_worst")[s:e], "worst_idx": slots.view(f"{st}_commit_worst_idx")[s:e]}
-                if indices:
-                    out["idx"] = slots.view(f"{st}_slots")[s:e]
-                ops.memory_scores(quans[st], x4.permute(0, 3, 1, 2), indices, out)
-                slots.view(f"{st}_psnr")[s:e] = ps
-            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
-            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
+    def on_batch(slots, s, e, k, fwd):
+        for st, x4, ps in zip(("rgb", "op"), model.bottleneck_inputs(), fwd.fused):
+            out = {"map": slots.view(f"{st}_commit_map")[s:e], "commit": slots.view(f"{st}_clip_comm")[s:e],
+                   "worst": slots.view(f"{st}_commit_worst")[s:e], "worst_idx": slots.view(f"{st}_commit_worst_idx")[s:e]}
+            if indices:
+                out["idx"] = slots.view(f"{st}_slots")[s:e]
+            ops.memory_scores(quans[st], x4.permute(0, 3, 1, 2), indices, out)
+            slots.view(f"{st}_psnr")[s:e] = ps
 
-    for k in range(len(batches)):
-        run(k, False)
-    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
-    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
-    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
-        for k in flagged:
-            run(k, True)
-            _count_fallback(model)
-        host = slots.flat.cpu().numpy()
-    names = [n for n, _ in sections if n not in ("comm", "flag")]
-    parts = []
-    for k, (s, e) in enumerate(batches):
-        part = {n: slots.view(n, host)[s:e] for n in names}
-        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
-        parts.append(part)
-    return assemble_localised(t, batches, parts)
+    return _run_pass(model, rgb_frames, op_frames, batches, sections, ints, on_batch)
 
 
 def evaluate_dataset_memory(model, videos, dataset_name: str = "synthetic", indices: bool = False,
@@ -554,26 +563,12 @@ def evaluate_dataset_memory(model, videos, dataset_name: str = "synthetic", indi
     `op_clip_comm_records` (the per-clip commit distance per frame: drop-ins for the `*_fea_comm_records` in
     `fuse_scores_auc`), `n_frames` and `map_files`.  `maps_dir`: one `NNNN.npz` per sub-video with the arrays of
     `memory_subvideo`."""
-    if device is None:
-        device = next(model.parameters()).device
-    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
-           "op_fea_comm_records": [], "rgb_clip_comm_records": [], "op_clip_comm_records": [], "n_frames": [], "map_files": []}
-    if maps_dir:
-        os.makedirs(maps_dir, exist_ok=True)
-    for v, (rgb, op) in enumerate(videos):
-        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
-        rec = memory_subvideo(model, rgb, op, batch, indices)
-        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
-        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
-        out["op_img_pred_records"].append(rec["op_psnr"])
-        out["op_fea_comm_records"].append(rec["op_comm"])
+    out = _new_records(dataset_name, "rgb_clip_comm_records", "op_clip_comm_records", "n_frames", "map_files")
+    for v, _, _, rec in _scored_subvideos(model, videos, out, lambda v, rgb, op: memory_subvideo(model, rgb, op, batch, indices),
+                                          device):
         out["rgb_clip_comm_records"].append(rec["rgb_clip_comm"])
         out["op_clip_comm_records"].append(rec["op_clip_comm"])
-        out["n_frames"].append(int(rgb.shape[0]))
-        if maps_dir:
-            path = os.path.join(maps_dir, f"{v:04d}.npz")
-            np.savez(path, **rec)
-            out["map_files"].append(path)
+        _write_maps(out, maps_dir, v, rec)
     return out
 
 
@@ -622,59 +617,23 @@ def quality_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, m
     device-to-host copy per sub-video; a batch whose S16 range flag is set is re-run with `exact=True`.  `predictions`:
     the testing hook of `localise_subvideo` - a list that receives (s, e, rgb_pred, op_pred, fused) of every batch."""
     from . import ops
-    t = rgb_frames.shape[0]
-    if op_frames.shape[0] != t - 1:
-        raise ValueError("a sub-video of T frames has T-1 flows")
-    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
-        raise ValueError("quality_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
-    batches = subvideo_batches(t, batch)
-    if not batches:
-        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
-    n_clip = batches[-1][1]
+    batches = _checked_batches("quality_subvideo", rgb_frames, op_frames, batch)
     sections = []
     for st, frames in (("rgb", rgb_frames), ("op", op_frames)):
-        sections += [(f"{st}_{k}", (n_clip,)) for k in ("ssim", "mse", "psnr")]
+        sections += [(f"{st}_{key}", ()) for key in ("ssim", "mse", "psnr")]
         if maps:
-            sections.append((f"{st}_ssim_map", (n_clip,) + tuple(frames.shape[2:])))
-    sections += [("comm", (len(batches), 2)), ("flag", (len(batches),))]
-    slots = _FlatSlots(sections, (), rgb_frames.device)
+            sections.append((f"{st}_ssim_map", tuple(frames.shape[2:])))
 
-    def run(k: int, exact: bool):
-        s, e = batches[k]
-        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
-        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
-        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
-        with torch.no_grad():
-            (rgb_out, op_out, diffs, _), *fused = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
-            flag = getattr(model, "last_overflow", None)
-            for st, pred, tgt in (("rgb", rgb_out, targets[0]), ("op", op_out, targets[1])):
-                out = {"ssim": slots.view(f"{st}_ssim")[s:e]}
-                if maps:
-                    out["map"] = slots.view(f"{st}_ssim_map")[s:e]
-                got = ops.ssim(pred, tgt, maps, out)
-                slots.view(f"{st}_mse")[s:e] = got["mse"]
-                slots.view(f"{st}_psnr")[s:e] = got["psnr"]
-            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
-            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
-        return (s, e, rgb_out, op_out, fused) if predictions is not None else None      # (else the frames are let go)
+    def on_batch(slots, s, e, k, fwd):
+        for st, pred, tgt in (("rgb", fwd.rgb_pred, fwd.targets[0]), ("op", fwd.op_pred, fwd.targets[1])):
+            out = {"ssim": slots.view(f"{st}_ssim")[s:e]}
+            if maps:
+                out["map"] = slots.view(f"{st}_ssim_map")[s:e]
+            got = ops.ssim(pred, tgt, maps, out)
+            slots.view(f"{st}_mse")[s:e] = got["mse"]
+            slots.view(f"{st}_psnr")[s:e] = got["psnr"]
 
-    done = [run(k, False) for k in range(len(batches))]
-    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
-    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
-    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
-        for k in flagged:
-            done[k] = run(k, True)
-            _count_fallback(model)
-        host = slots.flat.cpu().numpy()
-    if predictions is not None:
-        predictions.extend(done)
-    names = [n for n, _ in sections if n not in ("comm", "flag")]
-    parts = []
-    for k, (s, e) in enumerate(batches):
-        part = {n: slots.view(n, host)[s:e] for n in names}
-        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
-        parts.append(part)
-    return assemble_localised(t, batches, parts)
+    return _run_pass(model, rgb_frames, op_frames, batches, sections, (), on_batch, predictions)
 
 
 def evaluate_dataset_quality(model, videos, dataset_name: str = "synthetic", maps: bool = False,
@@ -685,28 +644,13 @@ def evaluate_dataset_quality(model, videos, dataset_name: str = "synthetic", map
     with `*_img_pred_records` from the fixed-order squared error (the reference's records for `loss_name` = psnr_error),
     plus `rgb_ssim_records` / `op_ssim_records` (ssim_error) and `rgb_mse_records` / `op_mse_records` (mse_error),
     `n_frames` and `map_files`.  `maps_dir`: one `NNNN.npz` per sub-video with the arrays of `quality_subvideo`."""
-    if device is None:
-        device = next(model.parameters()).device
-    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
-           "op_fea_comm_records": [], "rgb_ssim_records": [], "op_ssim_records": [], "rgb_mse_records": [],
-           "op_mse_records": [], "n_frames": [], "map_files": []}
-    if maps_dir:
-        os.makedirs(maps_dir, exist_ok=True)
-    for v, (rgb, op) in enumerate(videos):
-        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
-        rec = quality_subvideo(model, rgb, op, maps)
-        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
-        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
-        out["op_img_pred_records"].append(rec["op_psnr"])
-        out["op_fea_comm_records"].append(rec["op_comm"])
+    out = _new_records(dataset_name, "rgb_ssim_records", "op_ssim_records", "rgb_mse_records", "op_mse_records", "n_frames",
+                       "map_files")
+    for v, _, _, rec in _scored_subvideos(model, videos, out, lambda v, rgb, op: quality_subvideo(model, rgb, op, maps), device):
         for st in ("rgb", "op"):
             out[f"{st}_ssim_records"].append(rec[f"{st}_ssim"])
             out[f"{st}_mse_records"].append(rec[f"{st}_mse"])
-        out["n_frames"].append(int(rgb.shape[0]))
-        if maps_dir:
-            path = os.path.join(maps_dir, f"{v:04d}.npz")
-            np.savez(path, **rec)
-            out["map_files"].append(path)
+        _write_maps(out, maps_dir, v, rec)
     return out
 
 
@@ -1336,72 +1280,37 @@ def pixel_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mas
     `keep_maps`, a testing hook in the spirit of `predictions=`, asks for `pixel_map` [T,H,W] and `patch_map` [T,ph,pw]
     as they were scored."""
     from . import ops
-    t = rgb_frames.shape[0]
-    if op_frames.shape[0] != t - 1:
-        raise ValueError("a sub-video of T frames has T-1 flows")
-    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
-        raise ValueError("pixel_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
-    h, w = rgb_frames.shape[2:]
+    batches = _checked_batches("pixel_subvideo", rgb_frames, op_frames, batch)
+    t, (h, w) = rgb_frames.shape[0], rgb_frames.shape[2:]
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != rgb_frames.device:
         raise ValueError(f"pixel_subvideo: mask must be uint8 {(t, h, w)} on {rgb_frames.device}, got {mask.dtype} "
                          f"{tuple(mask.shape)} on {mask.device}")
-    batches = subvideo_batches(t, batch)
-    if not batches:
-        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
     mask = mask.contiguous()
     pooled = pool_mask(mask, patch)
     ph, pw = pooled.shape[1:]
-    n_clip = batches[-1][1]
     dev = rgb_frames.device
-    sections = [(f"rgb_{g}_{key}", (n_clip,)) for g in ("pix", "patch") for key in _PIXEL_KEYS]
-    sections += [("rgb_psnr", (n_clip,)), ("op_psnr", (n_clip,))]
+    sections = [(f"rgb_{g}_{key}", ()) for g in ("pix", "patch") for key in _PIXEL_KEYS] + [("rgb_psnr", ()), ("op_psnr", ())]
     if keep_maps:
-        sections += [("rgb_pixel_map", (n_clip, h, w)), ("rgb_patch_map", (n_clip, ph, pw))]
-    sections += [("comm", (len(batches), 2)), ("flag", (len(batches),))]
-    slots = _FlatSlots(sections, ("rgb_pix_m", "rgb_patch_m"), dev)
+        sections += [("rgb_pixel_map", (h, w)), ("rgb_patch_map", (ph, pw))]
     bmax = max(e - s for s, e in batches)
     buf = {"patch_sum": torch.empty((bmax, ph, pw), device=dev), "patch_mean": torch.empty((bmax, ph, pw), device=dev),
            "pixel": torch.empty((bmax, h, w), device=dev), "frame_sq": torch.empty(bmax, device=dev),
            "worst": torch.empty(bmax, device=dev), "worst_idx": torch.empty(bmax, device=dev, dtype=torch.int32)}
 
-    def run(k: int, exact: bool):
-        s, e = batches[k]
-        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
-        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
-        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
-        with torch.no_grad():
-            (rgb_out, _, diffs, _), _, op_psnr = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
-            flag = getattr(model, "last_overflow", None)
-            em = ops.error_maps(rgb_out, targets[0], patch, True, {key: v[:e - s] for key, v in buf.items()})
-            slots.view("rgb_psnr")[s:e] = em["psnr"]
-            slots.view("op_psnr")[s:e] = op_psnr
-            f0, f1 = s + RGB_LEN_CLIP - 1, e + RGB_LEN_CLIP - 1              # the frames these clips predict
-            for g, mp, mk in (("pix", em["pixel"], mask[f0:f1]), ("patch", em["patch_mean"], pooled[f0:f1])):
-                ops.pixel_scores(mp, mk, frac, {key: slots.view(f"rgb_{g}_{key}")[s:e] for key in _PIXEL_KEYS})
-            if keep_maps:
-                slots.view("rgb_pixel_map")[s:e] = em["pixel"]
-                slots.view("rgb_patch_map")[s:e] = em["patch_mean"]
-            slots.view("comm")[k, 0], slots.view("comm")[k, 1] = diffs[0].reshape(()), diffs[1].reshape(())
-            slots.view("flag")[k] = flag.reshape(()).to(torch.float32) if flag is not None else 0.0
+    def on_batch(slots, s, e, k, fwd):
+        em = ops.error_maps(fwd.rgb_pred, fwd.targets[0], patch, True, {key: v[:e - s] for key, v in buf.items()})
+        slots.view("rgb_psnr")[s:e] = em["psnr"]
+        slots.view("op_psnr")[s:e] = fwd.fused[1]
+        f0, f1 = s + RGB_LEN_CLIP - 1, e + RGB_LEN_CLIP - 1              # the frames these clips predict
+        for g, mp, mk in (("pix", em["pixel"], mask[f0:f1]), ("patch", em["patch_mean"], pooled[f0:f1])):
+            ops.pixel_scores(mp, mk, frac, {key: slots.view(f"rgb_{g}_{key}")[s:e] for key in _PIXEL_KEYS})
+        if keep_maps:
+            slots.view("rgb_pixel_map")[s:e] = em["pixel"]
+            slots.view("rgb_patch_map")[s:e] = em["patch_mean"]
 
-    for k in range(len(batches)):
-        run(k, False)
-    host = slots.flat.cpu().numpy()                     # the sub-video's one copy (and its one wait)
-    flagged = [k for k in range(len(batches)) if slots.view("flag", host)[k] != 0]
-    if flagged:                                          # S16 range guard: those batches again on the exact-fp32 kernels
-        for k in flagged:
-            run(k, True)
-            _count_fallback(model)
-        host = slots.flat.cpu().numpy()
-    names = [n for n, _ in sections if n not in ("comm", "flag")]
-    parts = []
-    for k, (s, e) in enumerate(batches):
-        part = {n: slots.view(n, host)[s:e] for n in names}
-        part["rgb_comm"], part["op_comm"] = slots.view("comm", host)[k]
-        parts.append(part)
-    rec = assemble_localised(t, batches, parts)
+    rec = _run_pass(model, rgb_frames, op_frames, batches, sections, ("rgb_pix_m", "rgb_patch_m"), on_batch)
     # (the rgb_ prefix chose the rgb stream's clip length in `assemble_localised`; the pixel figures carry none)
     return {(k[4:] if k[4:].startswith(("pix", "patch_")) else k): v for k, v in rec.items()}
 
@@ -1417,38 +1326,33 @@ def evaluate_dataset_pixel(model, videos, masks, dataset_name: str = "synthetic"
     `mask_videos` (the indices of the sub-videos that have a mask) and per sub-video the per-frame arrays of
     `pixel_subvideo` as lists by their names (`pix_m`, ..., `patch_max_out`; with `keep_maps` `pixel_map`, `patch_map`
     and the resized `mask`), None at a sub-video without a mask."""
-    if device is None:
-        device = next(model.parameters()).device
     keys = [f"{g}_{key}" for g in ("pix", "patch") for key in _PIXEL_KEYS] + (["pixel_map", "patch_map", "mask"] if keep_maps else [])
-    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
-           "op_fea_comm_records": [], "n_frames": [], "mask_videos": [], **{k: [] for k in keys}}
-    for v, (rgb, op) in enumerate(videos):
-        rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
+    out = _new_records(dataset_name, "n_frames", "mask_videos", *keys)
+
+    def score(v, rgb, op):
         t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
         if v >= len(masks):
             raise ValueError(f"evaluate_dataset_pixel: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
         mk = masks[v]
         if mk is None:
-            dm = torch.zeros((t, h, w), device=device, dtype=torch.uint8)
+            dm = torch.zeros((t, h, w), device=rgb.device, dtype=torch.uint8)
         else:
             mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
             if mk.dim() != 3 or mk.shape[0] != t:
                 raise ValueError(f"evaluate_dataset_pixel: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
             if mk.dtype not in (torch.uint8, torch.bool):
                 mk = mk != 0
-            dm = resize_mask(mk.to(device).view(torch.uint8) if mk.dtype == torch.bool else mk.to(device), (h, w)).contiguous()
+            dm = resize_mask(mk.to(rgb.device).view(torch.uint8) if mk.dtype == torch.bool else mk.to(rgb.device), (h, w)).contiguous()
         rec = pixel_subvideo(model, rgb, op, dm, patch, frac, keep_maps=keep_maps and mk is not None)
-        out["rgb_img_pred_records"].append(rec["rgb_psnr"])
-        out["rgb_fea_comm_records"].append(rec["rgb_comm"])
-        out["op_img_pred_records"].append(rec["op_psnr"])
-        out["op_fea_comm_records"].append(rec["op_comm"])
-        out["n_frames"].append(t)
-        if mk is not None:
+        if keep_maps and mk is not None:
+            rec["mask"] = dm.cpu().numpy()
+        return rec
+
+    for v, _, _, rec in _scored_subvideos(model, videos, out, score, device):
+        if masks[v] is not None:
             out["mask_videos"].append(v)
-            if keep_maps:
-                rec["mask"] = dm.cpu().numpy()
         for k in keys:
-            out[k].append(rec[k] if mk is not None else None)
+            out[k].append(rec[k] if masks[v] is not None else None)
     return out
 
 
@@ -1688,15 +1592,8 @@ def render_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, se
     `stats` (optional dict) receives `render_ms` (the render launches between events, summed), `render_batches`,
     `copies`, `rerun_batches`."""
     from . import ops
-    t = rgb_frames.shape[0]
-    if op_frames.shape[0] != t - 1:
-        raise ValueError("a sub-video of T frames has T-1 flows")
-    if not (rgb_frames.is_cuda and op_frames.is_cuda and rgb_frames.is_contiguous() and op_frames.is_contiguous()):
-        raise ValueError("render_subvideo reads a sub-video resident on the GPU (contiguous tensors): move it there first")
-    batches = subvideo_batches(t, batch)
-    if not batches:
-        raise ValueError(f"a sub-video needs at least {RGB_LEN_CLIP} frames")
-    lc = RGB_LEN_CLIP - 1
+    batches = _checked_batches("render_subvideo", rgb_frames, op_frames, batch)
+    t, lc = rgb_frames.shape[0], RGB_LEN_CLIP - 1
     if select is None:
         clips = list(range(batches[-1][1]))
     else:
@@ -1733,12 +1630,9 @@ def render_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, se
         k, lo, hi, _ = work[j]
         s, e = batches[k]
         slot = j % ring
-        rgb_in = clip_windows(rgb_frames, s, e, RGB_LEN_CLIP - 1)
-        op_in = clip_windows(op_frames, s, e, OP_LEN_CLIP - 1)
-        targets = (rgb_frames[s + RGB_LEN_CLIP - 1:e + RGB_LEN_CLIP - 1], op_frames[s + OP_LEN_CLIP - 1:e + OP_LEN_CLIP - 1])
+        fwd = _forward_batch(model, rgb_frames, op_frames, s, e, exact)
+        rgb_out, op_out, targets, flag = fwd.rgb_pred, fwd.op_pred, fwd.targets, fwd.overflow
         with torch.no_grad():
-            (rgb_out, op_out, _, _), *_ = model.forward_scored(rgb_in, op_in, *targets, defer_guard=True, exact=exact)
-            flag = getattr(model, "last_overflow", None)
             n = hi - lo
             out = dbuf[slot][head:head + n * per].view(n, ph, pw, 3)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1896,24 +1790,13 @@ def evaluate_dataset_panels(model, videos, dataset_name: str = "synthetic", pane
     import time
     if fmt not in ("png", "npy"):
         raise ValueError(f"evaluate_dataset_panels: format must be 'png' or 'npy', got {fmt!r}")
-    if device is None:
-        device = next(model.parameters()).device
-    out = {"dataset": dataset_name, "rgb_img_pred_records": [], "rgb_fea_comm_records": [], "op_img_pred_records": [],
-           "op_fea_comm_records": [], "rgb_patch_psnr_records": [], "n_frames": [], "panel_frames": [], "panel_files": []}
+    out = _new_records(dataset_name, "rgb_patch_psnr_records", "n_frames", "panel_frames", "panel_files")
     pool = OrderedWriterPool(workers) if panels_dir else None
     counters: dict = {}
     waited = 0.0
     try:
-        for v, (rgb, op) in enumerate(videos):
-            rgb, op = rgb.to(device, non_blocking=True).contiguous(), op.to(device, non_blocking=True).contiguous()
-            rec = localise_subvideo(model, rgb, op)
-            out["rgb_img_pred_records"].append(rec["rgb_psnr"])
-            out["rgb_fea_comm_records"].append(rec["rgb_comm"])
-            out["op_img_pred_records"].append(rec["op_psnr"])
-            out["op_fea_comm_records"].append(rec["op_comm"])
-            with np.errstate(divide="ignore"):
-                out["rgb_patch_psnr_records"].append((10.0 * np.log10(1.0 / rec["rgb_worst"].astype(np.float64))).astype(np.float32))
-            out["n_frames"].append(int(rgb.shape[0]))
+        for v, rgb, op, rec in _scored_subvideos(model, videos, out, lambda v, rgb, op: localise_subvideo(model, rgb, op), device):
+            out["rgb_patch_psnr_records"].append(_worst_patch_psnr(rec["rgb_worst"]))
             frames = select_frames(rec["rgb_psnr"], every, top)
             out["panel_frames"].append(frames)
             if panels_dir:

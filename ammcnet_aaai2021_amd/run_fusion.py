@@ -15,12 +15,9 @@ from __future__ import annotations
 import json
 
 import numpy as np
-import torch
 
-from . import harness, parallel, pipeline, synthetic
+from . import _entry, harness
 from .run_quality import build_parser as quality_parser
-from .run_test import synthetic_dataset, synthetic_raw_sources
-from .unet import get_twostream
 
 
 def build_parser():
@@ -57,29 +54,12 @@ def load_records(path: str, dataset_name: str):
 
 
 def evaluate(a, dev):
-    model = get_twostream((12, 6), (3, 2), a.embed_dim, a.n_embed, a.k)
-    if a.ckpt:
-        model.load_state_dict(torch.load(a.ckpt, map_location="cpu"), strict=True)
-    else:
-        model.load_state_dict(synthetic.make_twostream_state(embed_dim=a.embed_dim, n_embed=a.n_embed, k=a.k))
-    model = model.to(dev).eval()
-    model.precision = a.precision
-    streamed = bool(a.rgb_root and a.op_root or (a.synthetic and a.raw))
-    if a.data:
-        blob = torch.load(a.data, map_location="cpu")
-        sources, gt = blob["videos"], blob.get("gt")
-    elif a.rgb_root and a.op_root:
-        sources, gt = pipeline.list_subvideos(a.rgb_root, a.op_root), None
-    elif a.synthetic and a.raw:
-        sources, gt = synthetic_raw_sources(a.videos, a.frames)
-    elif a.synthetic:
-        sources, gt = synthetic_dataset(a.videos, a.frames, a.size)
-    else:
-        raise SystemExit("give --records, --data, --rgb_root/--op_root or --synthetic")
+    model = _entry.load_model(a, dev)
+    sources, gt, streamed = _entry.load_sources(a, "--records, --data, --rgb_root/--op_root or --synthetic")
     if gt is None:
         raise SystemExit("run_fusion needs frame labels: this data source has none (use --data with 'gt', or --records)")
     if streamed:
-        sources = pipeline.SubVideoStager(sources, dev, size=(a.size, a.size), shard=(0, 1), ahead=2)
+        sources = _entry.stager(a, sources, dev, streamed)
     return harness.evaluate_dataset_quality(model, sources, a.dataset_name, False, device=dev), gt
 
 
@@ -88,11 +68,7 @@ def main(argv=None):
     if a.maps_dir or a.ssim_maps:
         raise SystemExit("run_fusion writes no maps: --maps_dir / --ssim_maps belong to run_quality")
     channels = tuple(c.strip() for c in a.channels.split(",") if c.strip())
-    _, world, dev = parallel.init_distributed()
-    if world > 1:
-        raise SystemExit("run_fusion runs on one GPU (start a single process)")
-    if dev.type != "cuda":
-        raise SystemExit("run_fusion needs a GPU: the HIP path has no CPU fallback")
+    dev = _entry.one_gpu("run_fusion")
     if a.records:
         rec, gt = load_records(a.records, a.dataset_name)
     else:

@@ -26,13 +26,8 @@ from __future__ import annotations
 
 import argparse
 import json
-import time
 
-import torch
-
-from . import harness, parallel, pipeline, synthetic
-from .run_test import synthetic_dataset, synthetic_raw_sources
-from .unet import get_twostream
+from . import _entry, harness
 
 MAX_WORKERS = harness.OrderedWriterPool.MAX_WORKERS
 
@@ -67,21 +62,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--every", type=int, default=1, help="every N-th predicted frame")
     p.add_argument("--top", type=int, default=None, help="only the K lowest-PSNR frames of each sub-video")
     p.add_argument("--workers", type=int, default=8, help=f"writer threads (at most {MAX_WORKERS})")
-    # the model and the data source, as run_test takes them
-    p.add_argument("--dataset_name", default="ped2", choices=sorted(harness.LAM_MAP))
-    p.add_argument("--ckpt", default=None, help="state_dict of the reference's twostream generator (.pth)")
-    p.add_argument("--data", default=None, help="torch.save'd dict with 'videos' and optional 'gt'")
-    p.add_argument("--synthetic", action="store_true")
-    p.add_argument("--raw", action="store_true", help="with --synthetic: uint8 frames + flows through pipeline.SubVideoStager")
-    p.add_argument("--rgb_root", default=None, help="folder of sub-video folders of frames (jpg/png/.npy)")
-    p.add_argument("--op_root", default=None, help="folder of sub-video folders of flows (.flo/.npy)")
-    p.add_argument("--videos", type=int, default=4)
-    p.add_argument("--frames", type=int, default=60)
-    p.add_argument("--size", type=int, default=256)
-    p.add_argument("--precision", choices=("fp32", "s16"), default="s16")
-    p.add_argument("--embed_dim", type=int, default=64)
-    p.add_argument("--n_embed", type=int, default=256)
-    p.add_argument("--k", type=int, default=2)
+    _entry.add_common_args(p)
     return p
 
 
@@ -104,57 +85,27 @@ def parse_options(argv=None):
     if a.workers < 1:
         raise SystemExit(f"--workers needs at least 1, got {a.workers}")
     a.workers = min(a.workers, MAX_WORKERS)
-    if not (a.data or (a.rgb_root and a.op_root) or a.synthetic):
+    if not _entry.has_source(a):
         raise SystemExit("give --data, --rgb_root/--op_root or --synthetic")
     return a
 
 
 def main(argv=None):
     a = parse_options(argv)
-    _, world, dev = parallel.init_distributed()
-    if world > 1:
-        raise SystemExit("run_panels runs on one GPU: sharded picture writing is not implemented (start a single process)")
-    if dev.type != "cuda":
-        raise SystemExit("run_panels needs a GPU: the HIP path has no CPU fallback")
-    model = get_twostream((12, 6), (3, 2), a.embed_dim, a.n_embed, a.k)
-    if a.ckpt:
-        model.load_state_dict(torch.load(a.ckpt, map_location="cpu"), strict=True)
-    else:
-        model.load_state_dict(synthetic.make_twostream_state(embed_dim=a.embed_dim, n_embed=a.n_embed, k=a.k))
-    model = model.to(dev).eval()
-    model.precision = a.precision
-    streamed = bool(a.rgb_root and a.op_root or (a.synthetic and a.raw))
-    if a.data:
-        blob = torch.load(a.data, map_location="cpu")
-        sources, gt = blob["videos"], blob.get("gt")
-    elif a.rgb_root and a.op_root:
-        sources, gt = pipeline.list_subvideos(a.rgb_root, a.op_root), None
-    elif a.synthetic and a.raw:
-        sources, gt = synthetic_raw_sources(a.videos, a.frames)
-    else:
-        sources, gt = synthetic_dataset(a.videos, a.frames, a.size)
+    dev = _entry.one_gpu("run_panels", "sharded picture writing")
+    model = _entry.load_model(a, dev)
+    sources, gt, streamed = _entry.load_sources(a)
 
     def loop(srcs, panels_dir, stats):
-        # raw inputs stream: sub-video v + 1 / v + 2 are read, uploaded and resized on a side stream while v is scored
-        st = pipeline.SubVideoStager(srcs, dev, size=(a.size, a.size), shard=(0, 1), ahead=2) if streamed else None
+        st = _entry.stager(a, srcs, dev, streamed)
         rec = harness.evaluate_dataset_panels(model, st if streamed else srcs, a.dataset_name, panels_dir, a.format, a.every,
                                               a.top, a.workers, device=dev, stats=stats, tiles=a.tiles, flow_norm=a.flow_norm,
                                               heat_max=a.heat_max, alpha=a.alpha)
         return rec, st
-    loop(sources[:1], None, None)                                                # warm-up: plans, packs, pinned pools
-    torch.cuda.synchronize()
     stats: dict = {}
-    t0 = time.time()
-    rec, st = loop(sources, a.panels_dir, stats)
-    torch.cuda.synchronize()
-    used = time.time() - t0
-    n_pred = sum(t - harness.RGB_LEN_CLIP + 1 for t in rec["n_frames"])
-    out = {"dataset": a.dataset_name, "videos": len(rec["n_frames"]), "predicted_frames": n_pred, "gpus": 1,
-           "total_time_s": round(used, 3), "fps": round(n_pred / used, 2), "precision": a.precision,
-           "s16_fallbacks": getattr(model, "s16_fallbacks", 0)}
-    if st is not None:
-        out.update(host_read_s=round(st.host_seconds, 3), uploaded_MB=round(st.bytes_uploaded / 2**20, 1),
-                   staging="streamed: overlapped with the evaluation loop (total_time_s covers it)")
+    (rec, st), used = _entry.timed(loop, (sources[:1], None, None), (sources, a.panels_dir, stats))
+    out = _entry.base_report(a, model, rec["n_frames"], used, st, "evaluation")
+    n_pred = out["predicted_frames"]
     if gt is not None:
         out["auc"] = harness.fuse_scores_auc(rec, gt)["auc"]
         out["auc_note"] = "synthetic labels" if a.synthetic else "labels from --data"

@@ -19,14 +19,10 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import time
 
 import numpy as np
-import torch
 
-from . import harness, parallel, pipeline, synthetic
-from .run_test import synthetic_dataset, synthetic_raw_sources
-from .unet import get_twostream
+from . import _entry, harness, synthetic
 
 RAW_SIZE = (240, 360)        # `run_test.synthetic_raw_sources`' camera resolution
 
@@ -68,21 +64,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="the share of the ground-truth pixels that must be detected (2 5: the 40 %% rule)")
     p.add_argument("--normalise", default="none", choices=("none", "video"), help="divide a sub-video's scores by its largest value")
     p.add_argument("--mask_root", default=None, help="with --rgb_root / --op_root: folder of <sub-video folder name>.npy masks [T,h,w]")
-    # the model and the data source, as run_test takes them
-    p.add_argument("--dataset_name", default="ped2", choices=sorted(harness.LAM_MAP))
-    p.add_argument("--ckpt", default=None, help="state_dict of the reference's twostream generator (.pth)")
-    p.add_argument("--data", default=None, help="torch.save'd dict with 'videos' and optional 'gt'")
-    p.add_argument("--synthetic", action="store_true")
-    p.add_argument("--raw", action="store_true", help="with --synthetic: uint8 frames + flows through pipeline.SubVideoStager")
-    p.add_argument("--rgb_root", default=None, help="folder of sub-video folders of frames (jpg/png/.npy)")
-    p.add_argument("--op_root", default=None, help="folder of sub-video folders of flows (.flo/.npy)")
-    p.add_argument("--videos", type=int, default=4)
-    p.add_argument("--frames", type=int, default=60)
-    p.add_argument("--size", type=int, default=256)
-    p.add_argument("--precision", choices=("fp32", "s16"), default="s16")
-    p.add_argument("--embed_dim", type=int, default=64)
-    p.add_argument("--n_embed", type=int, default=256)
-    p.add_argument("--k", type=int, default=2)
+    _entry.add_common_args(p)
     return p
 
 
@@ -91,61 +73,32 @@ def main(argv=None):
     num, den = a.frac
     if not 1 <= num <= den <= 4096:
         raise SystemExit(f"--frac NUM DEN needs 1 <= NUM <= DEN <= 4096, got {num} {den}")
-    _, world, dev = parallel.init_distributed()
-    if world > 1:
-        raise SystemExit("run_pixel runs on one GPU: sharded pixel-level evaluation is not implemented (start a single process)")
-    if dev.type != "cuda":
-        raise SystemExit("run_pixel needs a GPU: the HIP path has no CPU fallback")
-    model = get_twostream((12, 6), (3, 2), a.embed_dim, a.n_embed, a.k)
-    if a.ckpt:
-        model.load_state_dict(torch.load(a.ckpt, map_location="cpu"), strict=True)
-    else:
-        model.load_state_dict(synthetic.make_twostream_state(embed_dim=a.embed_dim, n_embed=a.n_embed, k=a.k))
-    model = model.to(dev).eval()
-    model.precision = a.precision
-    streamed = bool(a.rgb_root and a.op_root or (a.synthetic and a.raw))
+    dev = _entry.one_gpu("run_pixel", "sharded pixel-level evaluation")
+    model = _entry.load_model(a, dev)
+    if not a.data and a.rgb_root and a.op_root and not a.mask_root:
+        raise SystemExit("--rgb_root / --op_root need --mask_root DIR for the pixel ground truth")
+    blob: dict = {}
+    sources, gt, streamed = _entry.load_sources(a, blob=blob)
     if a.data:
-        blob = torch.load(a.data, map_location="cpu")
-        sources, gt, masks = blob["videos"], blob.get("gt"), blob.get("masks")
+        masks = blob.get("masks")
         if masks is None:
             raise SystemExit("--data: the blob has no 'masks' list (one [T,h,w] array or None per sub-video)")
     elif a.rgb_root and a.op_root:
-        if not a.mask_root:
-            raise SystemExit("--rgb_root / --op_root need --mask_root DIR for the pixel ground truth")
-        sources, gt = pipeline.list_subvideos(a.rgb_root, a.op_root), None
         try:
             masks = masks_from_root(sorted(os.listdir(a.rgb_root)), a.mask_root)
         except ValueError as e:
             raise SystemExit(str(e)) from None
-    elif a.synthetic and a.raw:
-        sources, gt = synthetic_raw_sources(a.videos, a.frames)
-        masks = synthetic_masks(a.videos, a.frames, *RAW_SIZE)
-    elif a.synthetic:
-        sources, gt = synthetic_dataset(a.videos, a.frames, a.size)
-        masks = synthetic_masks(a.videos, a.frames, a.size, a.size)
     else:
-        raise SystemExit("give --data, --rgb_root/--op_root or --synthetic")
+        masks = synthetic_masks(a.videos, a.frames, *(RAW_SIZE if a.raw else (a.size, a.size)))
     if len(masks) != len(sources):
         raise SystemExit(f"{len(masks)} masks for {len(sources)} sub-videos")
 
     def loop(srcs, mks):
-        # raw inputs stream: sub-video v + 1 / v + 2 are read, uploaded and resized on a side stream while v is scored
-        st = pipeline.SubVideoStager(srcs, dev, size=(a.size, a.size), shard=(0, 1), ahead=2) if streamed else None
+        st = _entry.stager(a, srcs, dev, streamed)
         rec = harness.evaluate_dataset_pixel(model, st if streamed else srcs, mks, a.dataset_name, a.patch, (num, den), device=dev)
         return rec, st
-    loop(sources[:1], masks[:1])                                                 # warm-up: plans, packs, pinned pools
-    torch.cuda.synchronize()
-    t0 = time.time()
-    rec, st = loop(sources, masks)
-    torch.cuda.synchronize()
-    used = time.time() - t0
-    n_pred = sum(t - harness.RGB_LEN_CLIP + 1 for t in rec["n_frames"])
-    out = {"dataset": a.dataset_name, "videos": len(rec["n_frames"]), "predicted_frames": n_pred, "gpus": 1,
-           "total_time_s": round(used, 3), "fps": round(n_pred / used, 2), "precision": a.precision,
-           "s16_fallbacks": getattr(model, "s16_fallbacks", 0)}
-    if st is not None:
-        out.update(host_read_s=round(st.host_seconds, 3), uploaded_MB=round(st.bytes_uploaded / 2**20, 1),
-                   staging="streamed: overlapped with the pixel-level loop (total_time_s covers it)")
+    (rec, st), used = _entry.timed(loop, (sources[:1], masks[:1]), (sources, masks))
+    out = _entry.base_report(a, model, rec["n_frames"], used, st, "pixel-level")
     if gt is not None:
         out["auc"] = harness.fuse_scores_auc(rec, gt)["auc"]
     out.update(harness.pixel_level_auc(rec, a.normalise))

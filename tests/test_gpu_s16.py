@@ -182,6 +182,46 @@ def test_s16_overflow_in_a_middle_layer_at_256_through_the_harness():
     assert getattr(net2, "s16_fallbacks", 0) == 0
 
 
+def test_s16_overflow_through_the_evaluation_passes():
+    """the same guard through the pass driver (harness._run_pass): with the first layer's gamma blown up every batch of
+    `localise_subvideo`, `quality_subvideo`, `memory_subvideo` and `pixel_subvideo` is flagged and runs again on the
+    exact-fp32 kernels - one fallback per batch, records equal to the same pass on an all-fp32 model"""
+    from ammcnet_aaai2021_amd import harness
+    net, sd = _net()
+    big = _overflowing_state(sd)
+    net.load_state_dict(big)
+    ref, _ = _net()
+    ref.load_state_dict(big)
+    ref.precision = "fp32"
+    clean, _ = _net()
+    rgb = S.hashed_uniform("ovf-pass-vid", (11, 3, 64, 64)).to(DEV).contiguous()
+    op = S.hashed_normal("ovf-pass-flow", (10, 2, 64, 64), 2.0 / 256.0).to(DEV).contiguous()
+    mask = torch.zeros((11, 64, 64), device=DEV, dtype=torch.uint8)
+    n_batches = len(harness.subvideo_batches(11, 4))
+    assert n_batches == 2
+    passes = {"localise": lambda m: harness.localise_subvideo(m, rgb, op, batch=4),
+              "quality": lambda m: harness.quality_subvideo(m, rgb, op, batch=4),
+              "memory": lambda m: harness.memory_subvideo(m, rgb, op, batch=4),
+              "pixel": lambda m: harness.pixel_subvideo(m, rgb, op, mask, batch=4)}
+    for name, run in passes.items():
+        before = getattr(net, "s16_fallbacks", 0)
+        got, want = run(net), run(ref)
+        rose = getattr(net, "s16_fallbacks", 0) - before
+        print(f"{name}: s16_fallbacks rose by {rose} over {n_batches} batches")
+        assert set(got) == set(want)
+        for key in got:
+            if key.endswith(("_psnr", "_comm")):
+                # (equal up to the order of the float atomics that accumulate the squared errors inside the `outc` kernel)
+                err = float(np.max(np.abs(got[key].astype(np.float64) - want[key]) / np.abs(want[key])))
+                print(f"  {key}: max rel diff {err:.3g}, finite {bool(np.isfinite(got[key]).all())}")
+                assert np.isfinite(got[key]).all() and np.allclose(got[key], want[key], rtol=2e-6, atol=0), (name, key)
+            elif key.endswith("_worst_idx") or key in ("pix_m", "patch_m"):
+                assert got[key].dtype == np.int32 and np.array_equal(got[key], want[key]), (name, key)
+        assert rose == n_batches and net._engine.precision == "s16", name
+        run(clean)                                                    # with clean parameters nothing falls back
+    assert getattr(ref, "s16_fallbacks", 0) == 0 and getattr(clean, "s16_fallbacks", 0) == 0
+
+
 def test_fused_maxpool_matches_pool_kernel(monkeypatch):
     """the halo-patch kernel's second output (2x2 max-pool of the layer it just computed) against
     the stand-alone pooling kernel: all three encoder levels fuse at batch 8, 256x256.  The pooled VALUES are the same
