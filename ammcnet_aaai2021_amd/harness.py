@@ -1410,6 +1410,279 @@ def pixel_level_auc(rec: dict, normalise: str = "none") -> dict:
     return out
 
 
+# ---- region-based evaluation: detected regions against ground-truth regions -----------------
+# A pass of its own behind the evaluation forward and `ops.error_maps` (`ops.label_regions`, `ops.region_scores`,
+# csrc/region_scores.hip): nothing above is touched.  The region-based detection criterion (RBDC, Ramachandra and Jones):
+# at threshold t the detected regions are the connected components of {map >= t}; a ground-truth region is detected when
+# some detected region meets it with IoU >= num / den, and every detected region that matches no ground-truth region is
+# a false positive.  The track-based criterion (TBDC) counts a track as detected when at least alpha of its regions are.
+
+REGION_MAX_REGIONS = 32
+REGION_FRAME_CHUNK = 16      # frames per `ops.region_scores` call of `region_subvideo`
+REGION_TRACK_NOTE = ("tracks are derived, not annotated: ground-truth regions of consecutive frames that share a pixel "
+                     "belong to one track (transitive closure)")
+_REGION_KEYS = ("n_px", "n_comp", "n_fp", "hit")
+
+
+def region_thresholds(T: int = 64, spacing: str = "linear", floor: float = 1e-3) -> np.ndarray:
+    """T threshold values in (0, 1], increasing, fp32: "linear" i / T, "log" floor ** ((T - i) / T), i = 1..T - computed
+    in float64 and rounded to fp32 once.  A sub-video's thresholds are these values times its largest map value
+    (`normalise="video"`) or times `t_max` ("none")."""
+    if not isinstance(T, (int, np.integer)) or T < 1:
+        raise ValueError(f"region_thresholds: T must be an integer >= 1, got {T!r}")
+    i = np.arange(1, T + 1, dtype=np.float64)
+    if spacing == "linear":
+        v = i / float(T)
+    elif spacing == "log":
+        if not 0.0 < floor < 1.0:
+            raise ValueError(f"region_thresholds: the log floor must lie in (0, 1), got {floor!r}")
+        v = np.float64(floor) ** ((float(T) - i) / float(T))
+    else:
+        raise ValueError(f"region_thresholds: spacing must be 'linear' or 'log', got {spacing!r}")
+    return v.astype(np.float32)
+
+
+def region_tracks(labels_per_frame):
+    """Track ids from the overlap of consecutive label images.  `labels_per_frame`: [T, h, w] integers (or a sequence of
+    [h, w] images), 0 = background, r = region r of that frame (1..the frame's largest label).  Regions of frames f and
+    f + 1 belong to one track iff they share a pixel; tracks are the transitive closure, numbered from 0 in order of
+    their first region (frame, then label).  -> (tracks, n_tracks): tracks[f] an int array with the track id of region r
+    at [r - 1].  A frame without regions ends every track."""
+    frames = [np.asarray(f) for f in labels_per_frame]
+    counts = [int(f.max()) if f.size else 0 for f in frames]
+    start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    parent = list(range(int(start[-1])))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+    for f in range(len(frames) - 1):
+        a, b = frames[f], frames[f + 1]
+        both = (a > 0) & (b > 0)
+        if both.any():
+            for ra, rb in sorted(set(zip(a[both].tolist(), b[both].tolist()))):
+                x, y = find(int(start[f]) + ra - 1), find(int(start[f + 1]) + rb - 1)
+                if x != y:
+                    parent[max(x, y)] = min(x, y)
+    ids, out = {}, []
+    for f, c in enumerate(counts):
+        row = np.empty(c, dtype=np.int64)
+        for r in range(c):
+            row[r] = ids.setdefault(find(int(start[f]) + r), len(ids))
+        out.append(row)
+    return out, len(ids)
+
+
+def region_curve_area(fpr, rate) -> float:
+    """The area under a detection-rate curve that need not be monotone: the points (fpr, rate) of all thresholds; where
+    several share an fpr the largest rate stays; (0, r0) is added with r0 the largest rate at fpr 0 (0 if there is no
+    such point); sorted by fpr; a curve that ends below fpr 1 is extended flat to 1, one that passes 1 is cut there by
+    linear interpolation; the trapezoid area over [0, 1]."""
+    best = {0.0: 0.0}
+    for x, y in zip(np.asarray(fpr, dtype=np.float64).tolist(), np.asarray(rate, dtype=np.float64).tolist()):
+        if not (x >= 0.0 and y >= 0.0):
+            raise ValueError(f"region_curve_area: a point ({x}, {y}) outside the quadrant")
+        best[x] = max(best.get(x, 0.0), y)
+    xs = sorted(best)
+    pts = [(x, best[x]) for x in xs if x <= 1.0]
+    if xs[-1] > 1.0:
+        x1 = next(x for x in xs if x > 1.0)
+        (x0, y0), y1 = pts[-1], best[x1]
+        if x0 < 1.0:
+            pts.append((1.0, y0 + (y1 - y0) * (1.0 - x0) / (x1 - x0)))
+    elif pts[-1][0] < 1.0:
+        pts.append((1.0, pts[-1][1]))
+    return float(sum((b[0] - a[0]) * (a[1] + b[1]) / 2.0 for a, b in zip(pts, pts[1:])))
+
+
+def region_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mask: torch.Tensor, thresholds, patch: int = 16,
+                    iou=(1, 10), min_area: int = 1, connectivity: int = 8, normalise: str = "video", t_max=None,
+                    keep_maps: bool = False, min_gt_area: int = 1, batch: int = EVAL_BATCH,
+                    video: str = "") -> Dict[str, np.ndarray]:
+    """Are the detected regions the anomalous ones: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W] and mask uint8 (or bool)
+    [T,H,W] (nonzero = anomalous, at the frame size), contiguous and on the model's device, `thresholds` the fp32 [K]
+    values of `region_thresholds` -> per-frame numpy arrays of the sub-video.  Behind every forward
+    `ops.error_maps(rgb_pred, rgb_target, patch, pixel=True)` writes the batch's pixel map and patch means straight into
+    two per-sub-video device buffers.  After the last batch `ops.label_regions` numbers the ground-truth regions of
+    `mask` and of `pool_mask(mask, patch)` (`min_gt_area`), the thresholds become the values times the buffers' largest
+    value (`normalise="video"`: one fp32 multiply on the device, per map) or times `t_max` ("none"), and
+    `ops.region_scores` runs over the stored maps, REGION_FRAME_CHUNK frames at a time: frame t's prediction meets
+    mask[t].  Returned: `pix_n_px`, `pix_n_comp`, `pix_n_fp`, `pix_hit` (int32 [T, K]), `pix_gt_count` (int32 [T]),
+    `pix_labels` (uint8 [T,H,W]: the label images, which the tracks are derived from), `pix_thresholds` (fp32 [K], as
+    used), the same with the prefix `patch_`, and `rgb_psnr`, `rgb_comm`, `op_psnr`, `op_comm` as `pixel_subvideo` gives
+    them.  The first RGB_LEN_CLIP - 1 frames repeat frame RGB_LEN_CLIP - 1's numbers.  The region figures come to the
+    host in one copy per sub-video behind the driver's own; the maps leave the device only under `keep_maps`
+    (`pixel_map`, `patch_map`).  A frame with more than 32 ground-truth regions raises ValueError."""
+    from . import ops
+    if normalise not in ("video", "none"):
+        raise ValueError(f"region_subvideo: normalise must be 'video' or 'none', got {normalise!r}")
+    if normalise == "none" and (t_max is None or not np.isfinite(t_max) or t_max <= 0):
+        raise ValueError(f"region_subvideo: normalise='none' needs a finite t_max > 0, got {t_max!r}")
+    batches = _checked_batches("region_subvideo", rgb_frames, op_frames, batch)
+    t, (h, w) = rgb_frames.shape[0], rgb_frames.shape[2:]
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != rgb_frames.device:
+        raise ValueError(f"region_subvideo: mask must be uint8 {(t, h, w)} on {rgb_frames.device}, got {mask.dtype} "
+                         f"{tuple(mask.shape)} on {mask.device}")
+    dev, lc, n_clip = rgb_frames.device, RGB_LEN_CLIP, batches[-1][1]
+    values = torch.as_tensor(np.asarray(thresholds, dtype=np.float32).reshape(-1)).to(dev)
+    K = int(values.numel())
+    if K < 1:
+        raise ValueError("region_subvideo: no thresholds")
+    masks = {"pix": mask.contiguous()[lc - 1:], "patch": pool_mask(mask, patch).contiguous()[lc - 1:]}
+    ph, pw = masks["patch"].shape[1:]
+    maps = {"pix": torch.empty((n_clip, h, w), device=dev), "patch": torch.empty((n_clip, ph, pw), device=dev)}
+    bmax = max(e - s for s, e in batches)
+    buf = {"patch_sum": torch.empty((bmax, ph, pw), device=dev), "frame_sq": torch.empty(bmax, device=dev),
+           "worst": torch.empty(bmax, device=dev), "worst_idx": torch.empty(bmax, device=dev, dtype=torch.int32)}
+
+    def on_batch(slots, s, e, k, fwd):
+        out = {key: v[:e - s] for key, v in buf.items()}
+        out.update(pixel=maps["pix"][s:e], patch_mean=maps["patch"][s:e])
+        em = ops.error_maps(fwd.rgb_pred, fwd.targets[0], patch, True, out)
+        slots.view("rgb_psnr")[s:e] = em["psnr"]
+        slots.view("op_psnr")[s:e] = fwd.fused[1]
+
+    rec = _run_pass(model, rgb_frames, op_frames, batches, [("rgb_psnr", ()), ("op_psnr", ())], (), on_batch)
+    with torch.no_grad():
+        flat = torch.empty((2, 4 * K + 1, n_clip), device=dev, dtype=torch.int32)      # per map: 4 x [K] rows and the counts, by frame
+        labels, used = {}, {}
+        for gi, g in enumerate(("pix", "patch")):
+            lab = torch.empty_like(masks[g])
+            for s in range(0, n_clip, REGION_FRAME_CHUNK):
+                e = min(s + REGION_FRAME_CHUNK, n_clip)
+                ops.label_regions(masks[g][s:e], min_gt_area, connectivity, {"labels": lab[s:e], "count": flat[gi, 4 * K, s:e]})
+            scale = maps[g].max() if normalise == "video" else torch.tensor(float(t_max), device=dev, dtype=torch.float32)
+            used[g] = values * scale
+            for s in range(0, n_clip, REGION_FRAME_CHUNK):
+                e = min(s + REGION_FRAME_CHUNK, n_clip)
+                res = ops.region_scores(maps[g][s:e], lab[s:e], used[g], iou, min_area, connectivity)
+                for j, key in enumerate(_REGION_KEYS):
+                    flat[gi, j * K:(j + 1) * K, s:e] = res[key].t()
+            labels[g] = lab
+        host = flat.cpu().numpy()                        # the region figures' one copy
+
+    def frames_of(a: np.ndarray) -> np.ndarray:          # clip rows -> frame rows, with `assemble_localised`'s head fill
+        return np.concatenate([np.repeat(a[:1], lc - 1, axis=0), a])
+    for gi, g in enumerate(("pix", "patch")):
+        count = host[gi, 4 * K]
+        if (count < 0).any() or (host[gi, K:2 * K] < 0).any():
+            raise RuntimeError(f"region_subvideo: the labelling of sub-video {video!r} hit its round bound ({g} map)")
+        if (count > REGION_MAX_REGIONS).any():
+            f = int(np.argmax(count > REGION_MAX_REGIONS))
+            raise ValueError(f"sub-video {video!r}, frame {f + lc - 1}: {int(count[f])} ground-truth regions on the "
+                             f"{'frame' if g == 'pix' else 'patch grid'}, at most {REGION_MAX_REGIONS} are scored: drop "
+                             f"the specks with --min_gt_area")
+        for j, key in enumerate(_REGION_KEYS):
+            rec[f"{g}_{key}"] = frames_of(np.ascontiguousarray(host[gi, j * K:(j + 1) * K].T))
+        rec[f"{g}_gt_count"] = frames_of(count.copy())
+        rec[f"{g}_labels"] = frames_of(labels[g].cpu().numpy())
+        rec[f"{g}_thresholds"] = used[g].cpu().numpy()
+    if keep_maps:
+        rec["pixel_map"], rec["patch_map"] = frames_of(maps["pix"].cpu().numpy()), frames_of(maps["patch"].cpu().numpy())
+    return rec
+
+
+_REGION_REC_KEYS = tuple(f"{g}_{key}" for g in ("pix", "patch") for key in _REGION_KEYS + ("gt_count", "labels", "thresholds"))
+
+
+def evaluate_dataset_region(model, videos, masks, dataset_name: str = "synthetic", patch: int = 16, thresholds=None,
+                            iou=(1, 10), min_area: int = 1, connectivity: int = 8, normalise: str = "video", t_max=None,
+                            min_gt_area: int = 1, device=None, keep_maps: bool = False) -> dict:
+    """`evaluate_dataset` with `region_subvideo` in place of the scoring loop (one rank).  `videos` and `masks` as
+    `evaluate_dataset_pixel` takes them: masks[v] a uint8 / bool [T, h0, w0] array or tensor at any resolution (brought to
+    the frame size with `resize_mask`), or None - such a sub-video is evaluated for the frame records only and left out
+    of every region figure.  `thresholds`: fp32 values in (0, 1] (default `region_thresholds(64)`).  Returns the four
+    record lists of the reference, `n_frames`, `mask_videos` and per sub-video the arrays of `region_subvideo` as lists
+    by their names (with `keep_maps` also `pixel_map`, `patch_map` and the resized `mask`), None at a sub-video without
+    a mask."""
+    values = region_thresholds(64) if thresholds is None else np.asarray(thresholds, dtype=np.float32)
+    keys = list(_REGION_REC_KEYS) + (["pixel_map", "patch_map", "mask"] if keep_maps else [])
+    out = _new_records(dataset_name, "n_frames", "mask_videos", *keys)
+
+    def score(v, rgb, op):
+        t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
+        if v >= len(masks):
+            raise ValueError(f"evaluate_dataset_region: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
+        mk = masks[v]
+        if mk is None:
+            dm = torch.zeros((t, h, w), device=rgb.device, dtype=torch.uint8)
+        else:
+            mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
+            if mk.dim() != 3 or mk.shape[0] != t:
+                raise ValueError(f"evaluate_dataset_region: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
+            if mk.dtype not in (torch.uint8, torch.bool):
+                mk = mk != 0
+            dm = resize_mask(mk.to(rgb.device).view(torch.uint8) if mk.dtype == torch.bool else mk.to(rgb.device), (h, w)).contiguous()
+        rec = region_subvideo(model, rgb, op, dm, values, patch, iou, min_area, connectivity, normalise, t_max,
+                              keep_maps and mk is not None, min_gt_area, video=str(v))
+        if keep_maps and mk is not None:
+            rec["mask"] = dm.cpu().numpy()
+        return rec
+
+    for v, _, _, rec in _scored_subvideos(model, videos, out, score, device):
+        if masks[v] is not None:
+            out["mask_videos"].append(v)
+        for k in keys:
+            out[k].append(rec[k] if masks[v] is not None else None)
+    return out
+
+
+def region_level_auc(rec: dict, alpha=(1, 10)) -> dict:
+    """The region- and track-based figures of `evaluate_dataset_region`'s result over its `mask_videos`, the first
+    DECIDABLE_IDX frames of each dropped.  Per threshold index: RBDR = detected ground-truth regions / all of them, FPR =
+    false-positive regions / frames, TBDR = tracks with at least alpha = (num, den) of their regions detected / all
+    tracks (`region_tracks` over each sub-video's kept frames).  `rbdc`, `tbdc`: `region_curve_area` of (FPR, RBDR) and
+    (FPR, TBDR) on the pixel map; `rbdc_patch`, `tbdc_patch` on the patch map; `curves`: the arrays `fpr`, `rbdr`, `tbdr`
+    and their `_patch` forms; `n_gt_regions`, `n_tracks` (and `_patch`), `n_frames`, `track_note`.  Without a
+    ground-truth region the areas are None and `note` says why."""
+    a_num, a_den = (int(v) for v in alpha)
+    if not 1 <= a_num <= a_den:
+        raise ValueError(f"region_level_auc: alpha = (num, den) with 1 <= num <= den, got {alpha!r}")
+    out = {"track_note": REGION_TRACK_NOTE, "curves": {}}
+    d = DECIDABLE_IDX
+    for g, suffix in (("pix", ""), ("patch", "_patch")):
+        n_frames = n_gt = n_tracks = 0
+        fp = det = trk = None
+        for v in rec["mask_videos"]:
+            n_comp, n_fp, hit = (np.asarray(rec[f"{g}_{key}"][v])[d:].astype(np.int64) for key in ("n_comp", "n_fp", "hit"))
+            count = np.asarray(rec[f"{g}_gt_count"][v])[d:].astype(np.int64)
+            if (n_comp < 0).any():
+                raise ValueError(f"region_level_auc: sub-video {v} carries a failed labelling (n_comp = -1)")
+            if (count > REGION_MAX_REGIONS).any():
+                raise ValueError(f"region_level_auc: sub-video {v} has a frame with more than {REGION_MAX_REGIONS} regions")
+            K = n_fp.shape[1]
+            if fp is None:
+                fp, det, trk = np.zeros(K, np.int64), np.zeros(K, np.int64), np.zeros(K, np.int64)
+            n_frames += n_fp.shape[0]
+            fp += n_fp.sum(axis=0)
+            tracks, nt = region_tracks(np.asarray(rec[f"{g}_labels"][v])[d:])
+            hits = np.zeros((nt, K), np.int64)
+            size = np.zeros(nt, np.int64)
+            for f in range(count.shape[0]):
+                for r in range(int(count[f])):
+                    bit = (hit[f] >> r) & 1
+                    det += bit
+                    hits[tracks[f][r]] += bit
+                    size[tracks[f][r]] += 1
+            n_gt += int(count.sum())
+            n_tracks += nt
+            trk += (hits * a_den >= a_num * size[:, None]).sum(axis=0)
+        out["n_frames"] = n_frames
+        out["n_gt_regions" + suffix], out["n_tracks" + suffix] = n_gt, n_tracks
+        if n_gt == 0 or n_frames == 0:
+            out["rbdc" + suffix] = out["tbdc" + suffix] = None
+            out["note"] = "no ground-truth region among the scored frames: the curves have no rate"
+            continue
+        fpr, rbdr, tbdr = fp / float(n_frames), det / float(n_gt), trk / float(n_tracks)
+        out["curves"].update({"fpr" + suffix: fpr, "rbdr" + suffix: rbdr, "tbdr" + suffix: tbdr})
+        out["rbdc" + suffix], out["tbdc" + suffix] = region_curve_area(fpr, rbdr), region_curve_area(fpr, tbdr)
+    return out
+
+
 # ---- qualitative evaluation: prediction, flow and error panels (DESIGN.md section 5.22) ------------------------------
 # A pass of its own behind the evaluation forward (`ops.render_panels`, csrc/render.hip): finished uint8 pictures of the
 # frames, the colour-coded flows and the error heat maps.  The scoring loops above are not touched.

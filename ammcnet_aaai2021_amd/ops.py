@@ -415,6 +415,139 @@ def pixel_scores(map: torch.Tensor, mask: torch.Tensor, frac=(2, 5), out: dict |
     return res
 
 
+# ---- region-based evaluation (csrc/region_scores.hip) -----------------------------------------
+
+REGION_MAX_PIXELS = 1 << 22  # h * w of one sample
+REGION_MAX_REGIONS = 32      # ground-truth regions of one frame
+REGION_MAX_DEN = 4096
+REGION_WORKSPACE_BUDGET = 256 << 20   # bytes: `region_scores` splits its thresholds into launches that stay below it
+_REGION_KEYS = ("n_px", "n_comp", "n_fp", "hit")
+_region_ws: dict = {}        # (device, stream) -> the cached workspace
+
+
+def _region_sample_checks(what: str, tensors, min_area, connectivity):
+    """the [B, H, W] checks `label_regions` and `region_scores` share; tensors: [(name, tensor, dtypes)]"""
+    first = tensors[0][1]
+    for name, t, dtypes in tensors:
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype not in dtypes:
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be a [B, H, W] tensor of {' or '.join(str(d) for d in dtypes)}, got {got}")
+        if t.shape != first.shape:
+            raise ValueError(f"{what}: {name} is {tuple(t.shape)}, {tensors[0][0]} is {tuple(first.shape)}")
+    B, H, W = first.shape
+    if B < 1 or H < 1 or W < 1 or H * W > REGION_MAX_PIXELS:
+        raise ValueError(f"{what}: B, H, W >= 1 and H * W <= {REGION_MAX_PIXELS}, got {tuple(first.shape)}")
+    if not isinstance(min_area, int) or min_area < 1:
+        raise ValueError(f"{what}: min_area must be an integer >= 1, got {min_area!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity!r}")
+    for name, t, _ in tensors:
+        if not t[0].is_contiguous() or (B > 1 and t.stride(0) < H * W):
+            raise ValueError(f"{what}: {name}: a sample must be contiguous, with a batch stride >= H * W")
+    return B, H, W
+
+
+def _region_workspace(dev, nbytes: int) -> torch.Tensor:
+    """cached per (device, stream): launches on one stream run in order, so two calls never use it at once; it only grows"""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _region_ws.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        _region_ws.pop(key, None)
+        ws = _region_ws[key] = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.int32)
+    return ws
+
+
+def _bs(t: torch.Tensor, n: int) -> int:
+    return max(t.stride(0), n) if t.shape[0] == 1 else t.stride(0)
+
+
+def label_regions(mask: torch.Tensor, min_area: int = 1, connectivity: int = 8, out: dict | None = None) -> dict:
+    """The ground-truth regions of masks (csrc/region_scores.hip; definitions in include/ammc_hip.h).  `mask` uint8 or
+    bool [B, H, W] on the GPU, nonzero = anomalous, contiguous samples with any batch stride >= H * W.  Returns `labels`
+    uint8 [B, H, W] - 0 for the background, r = 1..32 for the r-th connected component (8- or 4-connectivity) with at
+    least `min_area` pixels, in raster order of the components' first pixels - and `count` int32 [B], the TRUE number
+    of kept components: components ranked beyond 32 are written as 0 and it is the caller's to refuse them.  One launch
+    on torch's current stream.  `out`: tensors to write into by those two keys (`labels` with contiguous samples)."""
+    B, H, W = _region_sample_checks("label_regions", [("mask", mask, (torch.uint8, torch.bool))], min_area, connectivity)
+    if not mask.is_cuda:
+        raise ValueError("label_regions: mask must be on the GPU; there is no CPU fallback")
+    dev = mask.device
+    out = dict(out) if out else {}
+    if set(out) - {"labels", "count"}:
+        raise ValueError(f"label_regions: `out` has no slot {sorted(set(out) - {'labels', 'count'})}")
+    labels, count = out.get("labels"), out.get("count")
+    if labels is None:
+        labels = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    elif (tuple(labels.shape) != (B, H, W) or labels.dtype != torch.uint8 or labels.device != dev or not labels[0].is_contiguous()
+          or (B > 1 and labels.stride(0) < H * W)):
+        raise ValueError(f"label_regions: out['labels'] must be uint8 {(B, H, W)} on {dev}, samples contiguous")
+    if count is None:
+        count = torch.empty((B,), device=dev, dtype=torch.int32)
+    elif tuple(count.shape) != (B,) or count.dtype != torch.int32 or count.device != dev or not count.is_contiguous():
+        raise ValueError(f"label_regions: out['count'] must be contiguous int32 {(B,)} on {dev}")
+    lib = _lib.load()
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    need = lib.ammc_region_workspace_bytes(B, 1, H, W)
+    ws = _region_workspace(dev, need)
+    _lib.check(lib.ammc_label_regions_u8(mask.data_ptr(), _bs(mask, H * W), B, H, W, min_area, connectivity, labels.data_ptr(),
+                                         _bs(labels, H * W), count.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(mask)),
+               "label_regions")
+    return {"labels": labels, "count": count}
+
+
+def region_scores(map: torch.Tensor, labels: torch.Tensor, thresholds: torch.Tensor, iou=(1, 10), min_area: int = 1,
+                  connectivity: int = 8, out: dict | None = None) -> dict:
+    """What the region-based detection criterion needs of score maps and label images (csrc/region_scores.hip;
+    definitions in include/ammc_hip.h).  `map` fp32 [B, H, W] on the GPU, higher = more anomalous; `labels` uint8
+    [B, H, W] as `label_regions` writes them (values above 32 count as background); each with contiguous samples and any
+    batch stride >= H * W.  `thresholds` fp32 [T] on the same device, any values in any order.  `iou` = (num, den),
+    1 <= num <= den <= 4096.  Per sample and threshold, int32 [B, T]: `n_px` (pixels with map >= t), `n_comp` (connected
+    components of them with at least `min_area` pixels), `n_fp` (those that match no region: |C n G| den >= num |C u G|
+    in 64-bit integers), `hit` (bit r - 1: some component matches region r).  Integers that depend on the sample's
+    values, its labels and the threshold alone.  One launch on torch's current stream per chunk of thresholds: the
+    workspace (12 bytes per pixel, sample and threshold) is cached per device and stays below REGION_WORKSPACE_BUDGET =
+    256 MiB (or one threshold's need, if that is more).  `n_comp` = -1 would report a labelling that hit its round
+    bound.  `out`: contiguous [B, T] int32 tensors to write into by the four keys."""
+    B, H, W = _region_sample_checks("region_scores", [("map", map, (torch.float32,)), ("labels", labels, (torch.uint8,))],
+                                    min_area, connectivity)
+    if not isinstance(thresholds, torch.Tensor) or thresholds.dim() != 1 or thresholds.dtype != torch.float32 or thresholds.numel() < 1:
+        raise ValueError("region_scores: thresholds must be a non-empty fp32 [T] tensor")
+    if not thresholds.is_contiguous():
+        raise ValueError("region_scores: thresholds must be contiguous")
+    try:
+        num, den = (int(v) for v in iou)
+    except (TypeError, ValueError):
+        raise ValueError(f"region_scores: iou must be a pair (num, den), got {iou!r}") from None
+    if not 1 <= num <= den <= REGION_MAX_DEN:
+        raise ValueError(f"region_scores: 1 <= num <= den <= {REGION_MAX_DEN}, got {iou!r}")
+    if not map.is_cuda or labels.device != map.device or thresholds.device != map.device:
+        raise ValueError("region_scores: map, labels and thresholds must be on one GPU; there is no CPU fallback")
+    dev, T = map.device, thresholds.numel()
+    out = dict(out) if out else {}
+    if set(out) - set(_REGION_KEYS):
+        raise ValueError(f"region_scores: `out` has no slot {sorted(set(out) - set(_REGION_KEYS))}")
+    res = {}
+    for key in _REGION_KEYS:
+        t = out.get(key)
+        if t is None:
+            t = torch.empty((B, T), device=dev, dtype=torch.int32)
+        elif tuple(t.shape) != (B, T) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"region_scores: out[{key!r}] must be contiguous int32 {(B, T)} on {dev}")
+        res[key] = t
+    lib = _lib.load()
+    per_t = lib.ammc_region_workspace_bytes(B, 1, H, W)
+    chunk = max(1, min(T, REGION_WORKSPACE_BUDGET // per_t))
+    ws = _region_workspace(dev, per_t * chunk)
+    for t0 in range(0, T, chunk):
+        tc = min(chunk, T - t0)
+        _lib.check(lib.ammc_region_scores_f32(_ptr(map), _bs(map, H * W), labels.data_ptr(), _bs(labels, H * W), B, H, W,
+                                              _ptr(thresholds[t0:]), tc, num, den, min_area, connectivity,
+                                              *(res[key][:, t0:].data_ptr() for key in _REGION_KEYS), T, ws.data_ptr(),
+                                              ws.numel() * 4, _stream(map)), "region_scores")
+    return res
+
+
 # ---- qualitative evaluation: panels of frames, colour-coded flows and error heat maps (csrc/render.hip) ----------
 
 RENDER_MAX_BATCH = 65535

@@ -927,6 +927,50 @@ int ammc_render_panels_u8(const float* rgb_pred, int64_t rp_bs, const float* rgb
 int ammc_flow_colour_u8(const float* flow, int64_t flow_bs, int32_t batch, int32_t h, int32_t w, float su, float sv,
                         const float* max_rad, float* workspace, uint8_t* out, int64_t out_bs, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Region-based evaluation (csrc/region_scores.hip): what the region-based detection criterion (RBDC, Ramachandra and
+ * Jones) needs of a score map and a frame's ground-truth regions, per sample and threshold, from a pass of its own.
+ *   map         fp32 [batch][h][w], higher = more anomalous; a sample contiguous, samples map_bs floats apart
+ *   mask        uint8 [batch][h][w], nonzero = anomalous; a sample contiguous, samples mask_bs bytes apart
+ *   labels      uint8 [batch][h][w], 0 = background, r = ground-truth region r; samples labels_bs bytes apart
+ *   thresholds  fp32 [t], any values in any order
+ * DEVICE arrays.  connectivity is 8 (a pixel touches its 8 neighbours) or 4 (W, E, N, S only).
+ * Detected regions.  At threshold thr the detected regions of a sample are the connected components of
+ *   {map >= thr}.  The comparison is the only floating-point operation on a map value; NaN compares false, -0.0 >= +0.0.
+ *   Components with fewer than min_area pixels are dropped: they are neither false positives nor able to detect.
+ * Ground-truth regions.  The connected components of {mask != 0} with the same connectivity and a min_area of their own,
+ *   numbered 1, 2, ... in raster order of each kept component's first pixel (its smallest flat index y * w + x).
+ *   ammc_label_regions_u8 writes that label image; count[b] is the TRUE number of kept components, also beyond 32;
+ *   components ranked beyond 32 are written as 0.
+ * Match.  Detected region C matches ground-truth region G iff |C n G| * den >= num * (|C| + |G| - |C n G|), evaluated in
+ *   64-bit integers (num / den = 1 / 10: IoU >= 0.1), 1 <= num <= den <= 4096.  |G| counts the label's pixels.
+ * ammc_region_scores_f32, per sample b and threshold index j, at [b * out_rs + j] of four int32 arrays:
+ *   n_px    the detected pixels (before min_area)
+ *   n_comp  the kept components
+ *   n_fp    the kept components that match no ground-truth region
+ *   hit     bit r - 1 is set iff some kept component matches region r, r = 1..32
+ *   Label values above 32 are treated as BACKGROUND.  All four are functions of the sample's map values, its label image
+ *   and the threshold alone - not of thread order, the batch size, the sample's place in the batch, a stride or an
+ *   alignment: every atomic is an integer count inside the workgroup's own workspace slice or LDS.
+ * One launch each, one workgroup per (sample, threshold) / per sample, labelling by a lock-free union-find that hangs
+ * the larger root below the smaller (the root of a component is its first pixel in raster order).  Every loop is
+ * bounded before it starts; should the bound on a union's retries ever be hit, n_comp = -1 (n_px = n_fp = hit = 0) or
+ * count = -1 reports it.  workspace: ammc_region_workspace_bytes(batch, t, h, w) bytes (3 int32 per pixel, sample and
+ * threshold; t = 1 for ammc_label_regions_u8), 4-byte aligned, contents irrelevant before and after;
+ * the function returns -1 for sizes the entries refuse.
+ * AMMC_EINVAL: a null pointer; batch, h, w, t or min_area < 1; h * w > 2^22; connectivity not 4 or 8; num < 1, den < num or
+ * den > 4096; with batch > 1 a batch stride < h * w or out_rs < t; map, thresholds, an int32 output or the workspace not
+ * 4-byte aligned; workspace_bytes too small.  AMMC_EUNSUP: batch * t >= 2^31.  All decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int64_t ammc_region_workspace_bytes(int32_t batch, int32_t t, int32_t h, int32_t w);
+int ammc_label_regions_u8(const uint8_t* mask, int64_t mask_bs, int32_t batch, int32_t h, int32_t w, int32_t min_area,
+                          int32_t connectivity, uint8_t* labels, int64_t labels_bs, int32_t* count, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int ammc_region_scores_f32(const float* map, int64_t map_bs, const uint8_t* labels, int64_t labels_bs, int32_t batch, int32_t h,
+                           int32_t w, const float* thresholds, int32_t t, int32_t num, int32_t den, int32_t min_area,
+                           int32_t connectivity, int32_t* n_px, int32_t* n_comp, int32_t* n_fp, int32_t* hit, int64_t out_rs,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
