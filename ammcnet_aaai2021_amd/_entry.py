@@ -1,5 +1,5 @@
 """What the evaluation entries (`run_test`, `run_maps`, `run_memory`, `run_quality`, `run_pixel`, `run_region`,
-`run_fusion`, `run_panels`) share: the model and data-source options, the device checks, the model, the four-way source selection, the
+`run_localise`, `run_fusion`, `run_panels`) share: the model and data-source options, the device checks, the model, the four-way source selection, the
 warm-up and timed loop, and the fields every entry's JSON line starts with."""
 from __future__ import annotations
 

@@ -191,6 +191,7 @@ SIGNATURES = {
     "ammc_region_workspace_bytes": (C.c_int64, [_i32] * 4),
     "ammc_label_regions_u8": (C.c_int, [_p, _i64] + [_i32] * 5 + [_p, _i64, _p, _p, _i64, _p]),
     "ammc_region_scores_f32": (C.c_int, [_p, _i64, _p, _i64] + [_i32] * 3 + [_p] + [_i32] * 5 + [_p, _p, _p, _p, _i64, _p, _i64, _p]),
+    "ammc_fuse_maps_f32": (C.c_int, [_p] * 5 + [_i32, _p] + [_i32] * 5 + [_p, _i64, _p, _i64, _p, _p, _p]),
 }
 
 _lib = None

@@ -1683,6 +1683,350 @@ def region_level_auc(rec: dict, alpha=(1, 10)) -> dict:
     return out
 
 
+# ---- fused localisation maps: flow error and memory commit beside the rgb error --------------
+# A pass of its own behind the evaluation forward (`ops.fuse_maps`, csrc/fuse_maps.hip): the rgb and flow error maps and
+# the two memory blocks' commit maps are kept on the device for a sub-video, then weighted, summed, smoothed by a box
+# window and scored by the pixel-level and region-based criteria above, once per weight vector.  Nothing above is touched.
+
+FUSE_CHANNELS = ("rgb_err", "op_err", "rgb_commit", "op_commit")
+FUSE_CELLS = (1, 1, 8, 8)    # frame pixels per value: the error maps are per pixel, the commit maps on the H/8 x W/8 bottleneck grid
+FUSE_MAX_SETTINGS = 8
+FUSE_FRAME_CHUNK = 16        # frames per `ops.fuse_maps` call of `fused_subvideo`
+FUSE_BUFFER_BUDGET = 4 << 30   # bytes of per-sub-video device buffers `fused_subvideo` accepts
+
+
+def _fuse_frame_size(sources, cells):
+    ref = next((c for c, cell in enumerate(cells) if cell == 1), None)
+    if ref is not None:
+        return tuple(int(v) for v in sources[ref].shape[1:])
+    return int(sources[0].shape[1]) * cells[0], int(sources[0].shape[2]) * cells[0]
+
+
+def fuse_maps_reference(sources, cells, coef, radius: int, patch: int) -> Dict[str, torch.Tensor]:
+    """the quantities of `ops.fuse_maps` in float64 with plain torch (any device; the reference of the tests).  `sources`:
+    [B, gh_c, gw_c] tensors, `cells` their cell sizes, `coef` [n_ch].  Source c is expanded blockily - frame pixel (y, x)
+    reads cell (min(y // cell, gh - 1), min(x // cell, gw - 1)) - `raw` is the coefficient-weighted sum, `pixel` its mean
+    over the in-frame part of the (2 radius + 1)^2 window, `patch_mean` the mean of `pixel` over each patch's true pixel
+    count, `frame_max` the largest `pixel` of a sample.  The frame size is that of the first source with cell 1 (else
+    grid * cell of source 0)."""
+    cells = [int(c) for c in cells]
+    h, w = _fuse_frame_size(sources, cells)
+    dev = sources[0].device
+    cf = torch.as_tensor(coef, dtype=torch.float64, device=dev) if not isinstance(coef, torch.Tensor) else coef.to(dev, torch.float64)
+    raw = None
+    for c, (s, cell) in enumerate(zip(sources, cells)):
+        ys = torch.clamp(torch.arange(h, device=dev) // cell, max=s.shape[1] - 1)
+        xs = torch.clamp(torch.arange(w, device=dev) // cell, max=s.shape[2] - 1)
+        term = cf[c] * s.to(torch.float64).index_select(1, ys).index_select(2, xs)
+        raw = term if raw is None else raw + term
+    ones = torch.ones((1, 1, h, w), dtype=torch.float64, device=dev)
+    r = int(radius)
+    padded = torch.nn.functional.pad(raw, (r, r, 0, 0))                      # sums of shifted slices: additions only
+    rows = sum(padded[:, :, d:d + w] for d in range(2 * r + 1))
+    padded = torch.nn.functional.pad(rows, (0, 0, r, r))
+    box = sum(padded[:, d:d + h, :] for d in range(2 * r + 1))
+    ys, xs = torch.arange(h, device=dev), torch.arange(w, device=dev)
+    ny = torch.clamp(ys + r, max=h - 1) - torch.clamp(ys - r, min=0) + 1
+    nx = torch.clamp(xs + r, max=w - 1) - torch.clamp(xs - r, min=0) + 1
+    pixel = box / (ny[:, None] * nx[None, :]).to(torch.float64)
+    ph, pw = -(-h // patch), -(-w // patch)
+    pad = (0, pw * patch - w, 0, ph * patch - h)
+    sums = torch.nn.functional.pad(pixel, pad).reshape(-1, ph, patch, pw, patch).sum(dim=(2, 4))
+    count = torch.nn.functional.pad(ones[0], pad).reshape(1, ph, patch, pw, patch).sum(dim=(2, 4))
+    return {"raw": raw, "pixel": pixel, "patch_mean": sums / count, "frame_max": pixel.amax(dim=(1, 2))}
+
+
+def check_fusion_weights(weights) -> List[List[float]]:
+    """`weights` as a list of 1..FUSE_MAX_SETTINGS settings of one length n_ch in 1..4, each value finite and >= 0 and not
+    all 0 (ValueError otherwise)"""
+    try:
+        rows = [[float(v) for v in r] for r in weights]
+    except (TypeError, ValueError):
+        raise ValueError(f"fusion weights: a list of weight vectors, got {weights!r}") from None
+    if not 1 <= len(rows) <= FUSE_MAX_SETTINGS:
+        raise ValueError(f"fusion weights: 1..{FUSE_MAX_SETTINGS} settings, got {len(rows)}")
+    n_ch = len(rows[0])
+    if not 1 <= n_ch <= len(FUSE_CHANNELS):
+        raise ValueError(f"fusion weights: 1..{len(FUSE_CHANNELS)} values per setting {FUSE_CHANNELS}, got {n_ch}")
+    for r in rows:
+        if len(r) != n_ch:
+            raise ValueError(f"fusion weights: every setting needs {n_ch} values, got {r}")
+        if not all(np.isfinite(v) and v >= 0 for v in r):
+            raise ValueError(f"fusion weights: finite values >= 0, got {r}")
+        if not any(v > 0 for v in r):
+            raise ValueError(f"fusion weights: a setting of all zeros scores nothing, got {r}")
+    return rows
+
+
+def fuse_coefficients(weights, maxima=None, normalise: str = "video", scales=None) -> torch.Tensor:
+    """The coefficients of one weight vector, fp32 [n_ch], computed on the device of `maxima` (a tensor: nothing waits for
+    it) or on the host.  "video": coef_c = fp32(w_c) / max_c with max_c the channel's largest value over the sub-video -
+    one fp32 division - and 0 where max_c == 0 (a channel that is zero everywhere adds nothing).  "none": coef_c =
+    fp32(w_c) * fp32(scale_c), `scales` defaulting to ones."""
+    w = (weights.to(torch.float32).reshape(-1) if isinstance(weights, torch.Tensor)
+         else torch.as_tensor(np.asarray(weights, dtype=np.float32).reshape(-1)))
+    if normalise == "video":
+        if maxima is None:
+            raise ValueError("fuse_coefficients: normalise='video' needs the channel maxima")
+        mx = torch.as_tensor(maxima, dtype=torch.float32).reshape(-1)
+        if mx.numel() != w.numel():
+            raise ValueError(f"fuse_coefficients: {w.numel()} weights for {mx.numel()} maxima")
+        w = w.to(mx.device)
+        return torch.where(mx == 0, torch.zeros_like(w), w / mx)
+    if normalise == "none":
+        sc = (torch.ones_like(w) if scales is None else scales.to(torch.float32).reshape(-1) if isinstance(scales, torch.Tensor)
+              else torch.as_tensor(np.asarray(scales, dtype=np.float32).reshape(-1)))
+        if sc.numel() != w.numel():
+            raise ValueError(f"fuse_coefficients: {w.numel()} weights for {sc.numel()} scales")
+        return w * sc.to(w.device)
+    raise ValueError(f"fuse_coefficients: normalise must be 'video' or 'none', got {normalise!r}")
+
+
+class _ByteSlots:
+    """one flat int32 device buffer carved into named sections of int32, fp32 or uint8 (each 16-byte aligned): the scoring
+    launches write straight into them and everything comes to the host by ONE copy"""
+
+    def __init__(self, sections, device):
+        self.layout, off = {}, 0
+        for name, shape, dtype in sections:
+            n = int(np.prod(shape)) if len(shape) else 1
+            words = n if dtype != torch.uint8 else (n + 3) // 4
+            self.layout[name] = (off, tuple(shape), dtype, n)
+            off += (words + 3) // 4 * 4
+        self.flat = torch.zeros(max(off, 4), device=device, dtype=torch.int32)
+
+    def view(self, name: str, host: Optional[np.ndarray] = None):
+        off, shape, dtype, n = self.layout[name]
+        words = n if dtype != torch.uint8 else (n + 3) // 4
+        if host is not None:
+            np_dtype = {torch.int32: np.int32, torch.float32: np.float32, torch.uint8: np.uint8}[dtype]
+            return host[off:off + words].view(np_dtype)[:n].reshape(shape)
+        v = self.flat[off:off + words]
+        return (v if dtype == torch.int32 else v.view(dtype))[:n].reshape(shape)
+
+
+def fused_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mask: Optional[torch.Tensor], weights, radius: int = 2,
+                   patch: int = 16, frac=(2, 5), thresholds=None, region: bool = True, normalise: str = "video", scales=None,
+                   iou=(1, 10), min_area: int = 1, connectivity: int = 8, t_max=None, keep_maps: bool = False,
+                   min_gt_area: int = 1, batch: int = EVAL_BATCH, video: str = "", budget: int = FUSE_BUFFER_BUDGET) -> dict:
+    """Do appearance, motion and the memories together find the anomaly: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W] and
+    mask uint8 (or bool) [T,H,W] (nonzero = anomalous, at the frame size), contiguous and on the model's device, `weights`
+    up to FUSE_MAX_SETTINGS weight vectors over the first n_ch of FUSE_CHANNELS.  One pass of the driver: behind every
+    forward `ops.error_maps(pixel=True)` writes the rgb pair's and the flow pair's per-pixel error and `ops.memory_scores`
+    both streams' commit maps (H/8 x W/8) straight into per-sub-video device buffers.  After the last batch (and the
+    driver's re-run of range-flagged batches) the channel maxima are taken on the device; then, per weight vector,
+    `fuse_coefficients` (on the device), `ops.fuse_maps` FUSE_FRAME_CHUNK frames at a time into ONE fused buffer that
+    every setting reuses, `ops.pixel_scores` on the fused pixel map with the masks and on its patch means with
+    `pool_mask(mask, patch)`, and with `region` `ops.region_scores` at `thresholds` (values in (0, 1], default
+    `region_thresholds(64)`) times the fused map's largest value - or times `t_max` where given - against the label
+    images `ops.label_regions` made once.  Frame t's prediction meets mask[t].  Returns `rgb_psnr`, `rgb_comm`,
+    `op_psnr`, `op_comm` (as `pixel_subvideo` gives them), `channel_max` (fp32 [n_ch]), `coef` (fp32 [G, n_ch]) and
+    `settings`: per weight vector the per-frame arrays `pix_m`, `pix_kth`, `pix_max_in`, `pix_max_out`, `patch_*`,
+    `frame_max`, and with `region` the arrays of `region_subvideo`.  The first RGB_LEN_CLIP - 1 frames repeat frame
+    RGB_LEN_CLIP - 1's numbers.  One device-to-host copy behind the driver's own; maps leave the device only under
+    `keep_maps` (`pixel_map`, `patch_map` per setting, `channel_maps` by channel name).  `mask=None`: only the four
+    records.  The buffers - three [clips, H, W] fp32 maps, the commit grids, the fused patch grid and the label images -
+    must fit in `budget` bytes (ValueError names the size)."""
+    from . import ops
+    rows = check_fusion_weights(weights)
+    n_ch, G = len(rows[0]), len(rows)
+    if normalise not in ("video", "none"):
+        raise ValueError(f"fused_subvideo: normalise must be 'video' or 'none', got {normalise!r}")
+    if t_max is not None and (not np.isfinite(t_max) or t_max <= 0):
+        raise ValueError(f"fused_subvideo: t_max must be finite and > 0, got {t_max!r}")
+    batches = _checked_batches("fused_subvideo", rgb_frames, op_frames, batch)
+    t, (h, w) = rgb_frames.shape[0], rgb_frames.shape[2:]
+    dev, lc, n_clip = rgb_frames.device, RGB_LEN_CLIP, batches[-1][1]
+    if h < 8 or w < 8:
+        raise ValueError(f"fused_subvideo: frames of at least 8 x 8 (the commit maps live on the H/8 x W/8 grid), got {h} x {w}")
+    scored = mask is not None
+    if scored:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != dev:
+            raise ValueError(f"fused_subvideo: mask must be uint8 {(t, h, w)} on {dev}, got {mask.dtype} {tuple(mask.shape)} "
+                             f"on {mask.device}")
+    values = torch.as_tensor(np.asarray(region_thresholds(64) if thresholds is None else thresholds, dtype=np.float32).reshape(-1)).to(dev)
+    K = int(values.numel())
+    if region and K < 1:
+        raise ValueError("fused_subvideo: no thresholds")
+    ph, pw, gh, gw = -(-h // patch), -(-w // patch), h // 8, w // 8
+    bmax = max(e - s for s, e in batches)
+    n_buf = n_clip if scored else bmax                   # without a mask nothing is kept: every batch reuses its slots
+    need = 4 * n_buf * (3 * h * w + 2 * gh * gw + ph * pw) + (n_buf * (h * w + ph * pw) if scored and region else 0)
+    if need > budget:
+        raise ValueError(f"fused_subvideo: sub-video {video!r} needs {need} bytes ({need / 2 ** 20:.1f} MiB) of device buffers "
+                         f"for {n_buf} clips of {h} x {w}, the budget is {budget} bytes: split the sub-video")
+    shapes = {"rgb_err": (h, w), "op_err": (h, w), "rgb_commit": (gh, gw), "op_commit": (gh, gw)}
+    maps = {name: torch.empty((n_buf,) + shapes[name], device=dev) for name in FUSE_CHANNELS}
+    buf = {"patch_sum": torch.empty((bmax, ph, pw), device=dev), "patch_mean": torch.empty((bmax, ph, pw), device=dev),
+           "frame_sq": torch.empty(bmax, device=dev), "worst": torch.empty(bmax, device=dev),
+           "worst_idx": torch.empty(bmax, device=dev, dtype=torch.int32)}
+    mbuf = {"commit": torch.empty(bmax, device=dev), "worst": torch.empty(bmax, device=dev),
+            "worst_idx": torch.empty(bmax, device=dev, dtype=torch.int32)}
+    quans = (model.rgb.vq_down3, model.op.vq_down3)
+    wdev = torch.tensor(rows, dtype=torch.float32).to(dev)                   # uploaded before the pass: nothing waits later
+    sdev = None if scales is None else torch.as_tensor(np.asarray(scales, dtype=np.float32).reshape(-1)).to(dev)
+    if sdev is not None and sdev.numel() != n_ch:
+        raise ValueError(f"fused_subvideo: {n_ch} weights per setting for {sdev.numel()} scales")
+
+    def on_batch(slots, s, e, k, fwd):
+        rows_ = slice(s, e) if scored else slice(0, e - s)
+        scratch = {key: v[:e - s] for key, v in buf.items()}
+        em = ops.error_maps(fwd.rgb_pred, fwd.targets[0], patch, True, dict(scratch, pixel=maps["rgb_err"][rows_]))
+        slots.view("rgb_psnr")[s:e] = em["psnr"]
+        slots.view("op_psnr")[s:e] = fwd.fused[1]
+        ops.error_maps(fwd.op_pred, fwd.targets[1], patch, True, dict(scratch, pixel=maps["op_err"][rows_]))
+        for name, quan, x4 in zip(("rgb_commit", "op_commit"), quans, model.bottleneck_inputs()):
+            ops.memory_scores(quan, x4.permute(0, 3, 1, 2), False, dict({key: v[:e - s] for key, v in mbuf.items()}, map=maps[name][rows_]))
+
+    rec = _run_pass(model, rgb_frames, op_frames, batches, [("rgb_psnr", ()), ("op_psnr", ())], (), on_batch)
+    if not scored:
+        return rec
+    names = FUSE_CHANNELS[:n_ch]
+    groups = ("pix", "patch")
+    masks = {"pix": mask.contiguous()[lc - 1:], "patch": pool_mask(mask, patch).contiguous()[lc - 1:]}
+    grid = {"pix": (h, w), "patch": (ph, pw)}
+    sections = [("channel_max", (n_ch,), torch.float32), ("coef", (G, n_ch), torch.float32)]
+    for gi in range(G):
+        sections.append((f"{gi}_frame_max", (n_clip,), torch.float32))
+        for g in groups:
+            sections += [(f"{gi}_{g}_{key}", (n_clip,), torch.int32 if key == "m" else torch.float32) for key in _PIXEL_KEYS]
+            if region:
+                sections += [(f"{gi}_{g}_{key}", (n_clip, K), torch.int32) for key in _REGION_KEYS]
+                sections.append((f"{gi}_{g}_thresholds", (K,), torch.float32))
+    if region:
+        for g in groups:
+            sections += [(f"{g}_gt_count", (n_clip,), torch.int32), (f"{g}_labels", (n_clip,) + grid[g], torch.uint8)]
+    with torch.no_grad():
+        res = _ByteSlots(sections, dev)
+        fused = {"pix": torch.empty((n_clip, h, w), device=dev), "patch": torch.empty((n_clip, ph, pw), device=dev)}
+        chunks = [(s, min(s + FUSE_FRAME_CHUNK, n_clip)) for s in range(0, n_clip, FUSE_FRAME_CHUNK)]
+        maxima = res.view("channel_max")
+        for c, name in enumerate(names):
+            maxima[c] = maps[name].amax()
+        if region:
+            for g in groups:
+                for s, e in chunks:
+                    ops.label_regions(masks[g][s:e], min_gt_area, connectivity,
+                                      {"labels": res.view(f"{g}_labels")[s:e], "count": res.view(f"{g}_gt_count")[s:e]})
+        kept = []
+        for gi, wv in enumerate(rows):
+            coef = res.view("coef")[gi]
+            coef.copy_(fuse_coefficients(wdev[gi], maxima, normalise, sdev))
+            for s, e in chunks:
+                ops.fuse_maps([maps[name][s:e] for name in names], FUSE_CELLS[:n_ch], coef, radius, patch,
+                              {"pixel": fused["pix"][s:e], "patch_mean": fused["patch"][s:e],
+                               "frame_max": res.view(f"{gi}_frame_max")[s:e]})
+                for g in groups:
+                    ops.pixel_scores(fused[g][s:e], masks[g][s:e], frac,
+                                     {key: res.view(f"{gi}_{g}_{key}")[s:e] for key in _PIXEL_KEYS})
+            if region:
+                for g in groups:
+                    scale = fused[g].max() if t_max is None else torch.tensor(float(t_max), device=dev, dtype=torch.float32)
+                    used = res.view(f"{gi}_{g}_thresholds")
+                    used.copy_(values * scale)
+                    for s, e in chunks:
+                        ops.region_scores(fused[g][s:e], res.view(f"{g}_labels")[s:e], used, iou, min_area, connectivity,
+                                          {key: res.view(f"{gi}_{g}_{key}")[s:e] for key in _REGION_KEYS})
+            if keep_maps:
+                kept.append((fused["pix"].cpu().numpy(), fused["patch"].cpu().numpy()))
+        host = res.flat.cpu().numpy()                    # the fused figures' one copy
+
+    def frames_of(a: np.ndarray) -> np.ndarray:          # clip rows -> frame rows, with `assemble_localised`'s head fill
+        return np.concatenate([np.repeat(a[:1], lc - 1, axis=0), a])
+    if region:
+        for g in groups:
+            count = res.view(f"{g}_gt_count", host)
+            if (count < 0).any():
+                raise RuntimeError(f"fused_subvideo: the labelling of sub-video {video!r} hit its round bound ({g} map)")
+            if (count > REGION_MAX_REGIONS).any():
+                f = int(np.argmax(count > REGION_MAX_REGIONS))
+                raise ValueError(f"sub-video {video!r}, frame {f + lc - 1}: {int(count[f])} ground-truth regions on the "
+                                 f"{'frame' if g == 'pix' else 'patch grid'}, at most {REGION_MAX_REGIONS} are scored: drop "
+                                 f"the specks with --min_gt_area")
+    rec["channel_max"], rec["coef"] = res.view("channel_max", host).copy(), res.view("coef", host).copy()
+    rec["settings"] = []
+    for gi in range(G):
+        one = {"frame_max": frames_of(res.view(f"{gi}_frame_max", host))}
+        for g in groups:
+            for key in _PIXEL_KEYS:
+                one[f"{g}_{key}"] = frames_of(res.view(f"{gi}_{g}_{key}", host))
+            if region:
+                if (res.view(f"{gi}_{g}_n_comp", host) < 0).any():
+                    raise RuntimeError(f"fused_subvideo: the labelling of sub-video {video!r} hit its round bound ({g} map)")
+                for key in _REGION_KEYS:
+                    one[f"{g}_{key}"] = frames_of(res.view(f"{gi}_{g}_{key}", host))
+                one[f"{g}_gt_count"] = frames_of(res.view(f"{g}_gt_count", host))
+                one[f"{g}_labels"] = frames_of(res.view(f"{g}_labels", host))
+                one[f"{g}_thresholds"] = res.view(f"{gi}_{g}_thresholds", host).copy()
+        if keep_maps:
+            one["pixel_map"], one["patch_map"] = frames_of(kept[gi][0]), frames_of(kept[gi][1])
+        rec["settings"].append(one)
+    if keep_maps:
+        rec["channel_maps"] = {name: frames_of(maps[name].cpu().numpy()) for name in names}
+    return rec
+
+
+def _frame_mask(who: str, masks, v: int, rgb: torch.Tensor) -> Optional[torch.Tensor]:
+    """masks[v] (a uint8 / bool / numeric [T, h0, w0] array or tensor, or None) on rgb's device at its frame size"""
+    t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
+    if v >= len(masks):
+        raise ValueError(f"{who}: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
+    mk = masks[v]
+    if mk is None:
+        return None
+    mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
+    if mk.dim() != 3 or mk.shape[0] != t:
+        raise ValueError(f"{who}: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
+    if mk.dtype not in (torch.uint8, torch.bool):
+        mk = mk != 0
+    mk = mk.to(rgb.device)
+    return resize_mask(mk.view(torch.uint8) if mk.dtype == torch.bool else mk, (h, w)).contiguous()
+
+
+def evaluate_dataset_fused(model, videos, masks, weights, dataset_name: str = "synthetic", radius: int = 2, patch: int = 16,
+                           frac=(2, 5), thresholds=None, region: bool = True, normalise: str = "video", scales=None,
+                           iou=(1, 10), min_area: int = 1, connectivity: int = 8, t_max=None, min_gt_area: int = 1, device=None,
+                           keep_maps: bool = False, budget: int = FUSE_BUFFER_BUDGET) -> dict:
+    """`evaluate_dataset` with `fused_subvideo` in place of the scoring loop (one rank): ONE forward of the data set
+    scores every weight vector of `weights`.  `videos` and `masks` as `evaluate_dataset_pixel` takes them (a None mask:
+    the sub-video is evaluated for the frame records only and left out of every figure).  Returns {"weights": the
+    settings as lists, "settings": [rec_0, ...]}: rec_g carries the keys of `evaluate_dataset_pixel`'s result and, with
+    `region`, of `evaluate_dataset_region`'s - so `pixel_level_auc(rec_g)` and `region_level_auc(rec_g)` work unchanged -
+    plus `frame_max`; the four reference record lists, `n_frames` and `mask_videos` are the SAME list objects in every
+    rec_g.  With `keep_maps` rec_g also holds `pixel_map`, `patch_map` and `mask`, and the result `channel_maps` (per
+    sub-video a dict by channel name, None without a mask), `channel_max` and `coef`."""
+    rows = check_fusion_weights(weights)
+    keys = ["frame_max"] + [f"{g}_{key}" for g in ("pix", "patch") for key in _PIXEL_KEYS] + (list(_REGION_REC_KEYS) if region else [])
+    keys += ["pixel_map", "patch_map", "mask"] if keep_maps else []
+    base = _new_records(dataset_name, "n_frames", "mask_videos")
+    recs = [dict(base, **{k: [] for k in keys}) for _ in rows]      # (a shallow copy: the lists of `base` are shared)
+    out = {"weights": rows, "settings": recs, "channel_max": [], "coef": []}
+    if keep_maps:
+        out["channel_maps"] = []
+    held = {}
+
+    def score(v, rgb, op):
+        held["mask"] = dm = _frame_mask("evaluate_dataset_fused", masks, v, rgb)
+        return fused_subvideo(model, rgb, op, dm, rows, radius, patch, frac, thresholds, region, normalise, scales, iou, min_area,
+                              connectivity, t_max, keep_maps and dm is not None, min_gt_area, video=str(v), budget=budget)
+
+    for v, _, _, rec in _scored_subvideos(model, videos, base, score, device):
+        has = held["mask"] is not None
+        if has:
+            base["mask_videos"].append(v)
+        host_mask = held["mask"].cpu().numpy() if has and keep_maps else None
+        for gi, one in enumerate(recs):
+            for k in keys:
+                one[k].append((host_mask if k == "mask" else rec["settings"][gi][k]) if has else None)
+        out["channel_max"].append(rec["channel_max"] if has else None)
+        out["coef"].append(rec["coef"] if has else None)
+        if keep_maps:
+            out["channel_maps"].append(rec["channel_maps"] if has else None)
+    return out
+
+
 # ---- qualitative evaluation: prediction, flow and error panels (DESIGN.md section 5.22) ------------------------------
 # A pass of its own behind the evaluation forward (`ops.render_panels`, csrc/render.hip): finished uint8 pictures of the
 # frames, the colour-coded flows and the error heat maps.  The scoring loops above are not touched.

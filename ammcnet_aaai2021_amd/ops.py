@@ -9,6 +9,7 @@ parity test (tests/test_gpu_parity.py, tests/test_gpu_s16.py).  No ATen compute 
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -545,6 +546,104 @@ def region_scores(map: torch.Tensor, labels: torch.Tensor, thresholds: torch.Ten
                                               _ptr(thresholds[t0:]), tc, num, den, min_area, connectivity,
                                               *(res[key][:, t0:].data_ptr() for key in _REGION_KEYS), T, ws.data_ptr(),
                                               ws.numel() * 4, _stream(map)), "region_scores")
+    return res
+
+
+# ---- fused localisation maps (csrc/fuse_maps.hip) ----------------------------------------------
+
+FUSE_MAX_CHANNELS = 4
+FUSE_MAX_RADIUS = 8
+FUSE_MAX_PIXELS = 1 << 28    # h * w of one sample
+FUSE_TILE = (32, 64)         # the tile of csrc/fuse_maps.hip: the workspace holds one float per tile and sample
+_FUSE_KEYS = ("pixel", "patch_mean", "frame_max")
+_fuse_ws: dict = {}          # (device, stream) -> the cached workspace
+
+
+def fuse_maps(sources, cells, coef: torch.Tensor, radius: int = 0, patch: int = 16, out: dict | None = None) -> dict:
+    """Several score maps of different resolution -> one smoothed map (csrc/fuse_maps.hip; definitions in
+    include/ammc_hip.h).  `sources`: 1..4 fp32 [B, gh_c, gw_c] tensors on one GPU, higher = more anomalous, a sample's rows
+    and columns contiguous, any batch stride (nothing is copied); `cells`: per source the integer edge >= 1 of the square
+    of frame pixels one value covers.  The frame size is that of the first source with cell 1, or, without one,
+    (gh_0 * cell_0, gw_0 * cell_0); every gh_c must be H // cell_c or ceil(H / cell_c) and >= 1, gw_c alike.  `coef`: fp32
+    [n_ch] on the same device (computed there: no host wait).  `radius` 0..8: a count-normalised (2 radius + 1)^2 box mean
+    without padding; `patch` 8, 16 or 32.  Returns `pixel` [B, H, W] (the weighted sum of the blockily expanded sources,
+    smoothed), `patch_mean` [B, ph, pw] (its means over `error_maps`' patch grid, true pixel counts) and `frame_max` [B]
+    (its largest value, bit for bit).  fp32 without contraction, sums that only add, no atomics: a sample's outputs do
+    not depend on the batch it is in, equal inputs give equal bits.  Two launches on torch's current stream.  `out`:
+    tensors to write into by the same keys (views of per-sub-video buffers) - maps with contiguous samples and any batch
+    stride, `frame_max` contiguous."""
+    if not isinstance(sources, (list, tuple)) or not 1 <= len(sources) <= FUSE_MAX_CHANNELS:
+        raise ValueError(f"fuse_maps: 1..{FUSE_MAX_CHANNELS} source maps, got "
+                         f"{len(sources) if isinstance(sources, (list, tuple)) else type(sources).__name__}")
+    n_ch = len(sources)
+    try:
+        cells = [int(c) for c in cells]
+    except (TypeError, ValueError):
+        raise ValueError(f"fuse_maps: cells must be {n_ch} integers, got {cells!r}") from None
+    if len(cells) != n_ch or min(cells) < 1:
+        raise ValueError(f"fuse_maps: one cell size >= 1 per source, got {cells!r} for {n_ch} sources")
+    for c, s in enumerate(sources):
+        if not isinstance(s, torch.Tensor) or s.dim() != 3 or s.dtype != torch.float32:
+            got = f"{s.dtype} {tuple(s.shape)}" if isinstance(s, torch.Tensor) else type(s).__name__
+            raise ValueError(f"fuse_maps: source {c} must be an fp32 [B, gh, gw] tensor, got {got}")
+    B = sources[0].shape[0]
+    ref = next((c for c in range(n_ch) if cells[c] == 1), None)
+    H, W = sources[ref].shape[1:] if ref is not None else (sources[0].shape[1] * cells[0], sources[0].shape[2] * cells[0])
+    H, W = int(H), int(W)
+    if B < 1 or H < 1 or W < 1 or H * W > FUSE_MAX_PIXELS:
+        raise ValueError(f"fuse_maps: B, H, W >= 1 and H * W <= {FUSE_MAX_PIXELS}, got B = {B}, a {H} x {W} frame")
+    for c, s in enumerate(sources):
+        _, gh, gw = s.shape
+        if s.shape[0] != B:
+            raise ValueError(f"fuse_maps: source {c} has batch {s.shape[0]}, source 0 has {B}")
+        if gh < 1 or gw < 1 or gh not in (H // cells[c], -(-H // cells[c])) or gw not in (W // cells[c], -(-W // cells[c])):
+            raise ValueError(f"fuse_maps: source {c} is a {gh} x {gw} grid: a {H} x {W} frame in cells of {cells[c]} has "
+                             f"{H // cells[c]} or {-(-H // cells[c])} rows and {W // cells[c]} or {-(-W // cells[c])} columns (>= 1)")
+        if not s[0].is_contiguous() or (B > 1 and s.stride(0) < gh * gw):
+            raise ValueError(f"fuse_maps: source {c}: a sample must be contiguous, with a batch stride >= gh * gw")
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius <= FUSE_MAX_RADIUS:
+        raise ValueError(f"fuse_maps: radius must be an integer in 0..{FUSE_MAX_RADIUS}, got {radius!r}")
+    if patch not in ERROR_MAP_PATCHES:
+        raise ValueError(f"fuse_maps: patch must be one of {ERROR_MAP_PATCHES}, got {patch!r}")
+    if not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32 or tuple(coef.shape) != (n_ch,) or not coef.is_contiguous():
+        raise ValueError(f"fuse_maps: coef must be a contiguous fp32 [{n_ch}] tensor")
+    dev = sources[0].device
+    if coef.device != dev or any(s.device != dev for s in sources):
+        raise ValueError("fuse_maps: the sources and coef must be on one device")
+    ph, pw = (H + patch - 1) // patch, (W + patch - 1) // patch
+    want = {"pixel": (B, H, W), "patch_mean": (B, ph, pw), "frame_max": (B,)}
+    out = dict(out) if out else {}
+    if set(out) - set(want):
+        raise ValueError(f"fuse_maps: `out` has no slot {sorted(set(out) - set(want))}")
+    res = {}
+    for key, shape in want.items():
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=torch.float32)
+        elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"fuse_maps: out[{key!r}] must be fp32 {shape} on {dev}")
+        elif t.dim() == 1 and not t.is_contiguous():
+            raise ValueError(f"fuse_maps: out[{key!r}] must be contiguous")
+        elif t.dim() == 3 and (not t[0].is_contiguous() or (B > 1 and t.stride(0) < shape[1] * shape[2])):
+            raise ValueError(f"fuse_maps: out[{key!r}]: the map of a sample must be contiguous, with a batch stride >= its size")
+        res[key] = t
+    if dev.type != "cuda":
+        raise ValueError("fuse_maps: the sources and coef must be on the GPU; there is no CPU fallback")
+    lib = _lib.load()
+    tiles = B * (-(-H // FUSE_TILE[0])) * (-(-W // FUSE_TILE[1]))
+    wkey = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _fuse_ws.get(wkey)                                   # launches on one stream run in order; it only grows
+    if ws is None or ws.numel() < tiles:
+        ws = _fuse_ws[wkey] = torch.empty(tiles, device=dev, dtype=torch.float32)
+    ptrs = (ctypes.c_void_p * n_ch)(*(s.data_ptr() for s in sources))
+    strides = (ctypes.c_int64 * n_ch)(*(_bs(s, s.shape[1] * s.shape[2]) for s in sources))
+    ghs = (ctypes.c_int32 * n_ch)(*(s.shape[1] for s in sources))
+    gws = (ctypes.c_int32 * n_ch)(*(s.shape[2] for s in sources))
+    cls = (ctypes.c_int32 * n_ch)(*cells)
+    px, pm = res["pixel"], res["patch_mean"]
+    _lib.check(lib.ammc_fuse_maps_f32(ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(ghs), ctypes.addressof(gws), ctypes.addressof(cls),
+                                      n_ch, _ptr(coef), B, H, W, radius, patch, _ptr(px), _bs(px, H * W), _ptr(pm), _bs(pm, ph * pw),
+                                      _ptr(res["frame_max"]), _ptr(ws), _stream(sources[0])), "fuse_maps")
     return res
 
 

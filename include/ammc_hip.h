@@ -971,6 +971,48 @@ int ammc_region_scores_f32(const float* map, int64_t map_bs, const uint8_t* labe
                            int32_t connectivity, int32_t* n_px, int32_t* n_comp, int32_t* n_fp, int32_t* hit, int64_t out_rs,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused localisation maps (csrc/fuse_maps.hip): several score maps of different resolution become one smoothed map of
+ * the frame's size, its patch means and its largest value, from a pass of its own.
+ *   src[c]   fp32 [batch][gh[c]][gw[c]], c < n_ch (1..4); a sample's rows and columns contiguous, samples src_bs[c]
+ *            floats apart.  cell[c] >= 1 is the edge of the square of frame pixels one source value covers:
+ *            gh[c] is h / cell[c] or ceil(h / cell[c]) and >= 1, gw[c] the same of w.  src, src_bs, gh, gw and cell are
+ *            HOST arrays of n_ch entries, read during the call; the maps themselves are DEVICE arrays.
+ *   coef     fp32 [n_ch], a DEVICE array (the caller computes it on the device without a host wait)
+ *   radius   0..8: the box window is (2 radius + 1)^2;  patch: 8, 16 or 32
+ * All arithmetic is fp32 and no product is contracted into a sum.
+ *   m_c(b, y, x)   = src[c][b][min(y / cell[c], gh[c] - 1)][min(x / cell[c], gw[c] - 1)]      (blocky, no interpolation)
+ *   raw(b, y, x)   = ((coef[0] * m_0 + coef[1] * m_1) + coef[2] * m_2) + coef[3] * m_3, truncated to n_ch terms
+ *   pixel[b][y][x] = the sum of raw over the pixels (y', x') of the frame with |y' - y| <= radius and |x' - x| <= radius,
+ *                    divided by their number: a count-normalised mean, no zero padding.  Per row of the window the
+ *                    columns are added left to right, the row sums top to bottom, each starting from its first term,
+ *                    then one division: sums only add (no sliding-window subtraction), so with non-negative inputs a
+ *                    value is within (2 n_ch + 4 radius) * 2^-24 relative of the real one.  With n_ch = 1, coef = 1,
+ *                    cell = 1 and radius = 0, pixel equals the source bit for bit.
+ *   patch_mean[b][i][j] = the sum of pixel over patch (i, j) of ammc_error_maps_f32's grid (patch x patch pixels
+ *                    anchored at (0, 0), the last row / column ragged) divided by its true pixel count; per image row
+ *                    quads (p0 + p1) + (p2 + p3) left to right, then the rows top to bottom.  [batch][ph][pw], samples
+ *                    pm_bs floats apart.
+ *   frame_max[b]   = the largest pixel value of the sample, one of them bit for bit.
+ * pixel is [batch][h][w], a sample contiguous, samples px_bs floats apart (16-byte stores where the base, px_bs and w
+ * are multiples of 4 floats, 4-byte stores otherwise: the same bits).
+ * The kernel checks no values: NaN and infinities propagate through the sums, and a NaN pixel makes frame_max NaN.
+ * Callers pass non-negative finite maps and coefficients.
+ * Two launches: one 256-thread workgroup per 32 x 64 tile of a sample (whole patches live in one workgroup; the tile
+ * and its halo are staged in LDS once), then one workgroup per sample over the tiles' maxima.  workspace: batch *
+ * ceil(h / 32) * ceil(w / 64) floats, contents irrelevant before and after.  No atomics; every output is written once
+ * by one thread and is a function of the sample's own values, coef, the sizes, radius and patch - not of the batch
+ * size, the sample's place in the batch, a stride or an alignment.  Equal inputs give equal bits.
+ * AMMC_EINVAL: a null pointer; n_ch outside 1..4; batch, h or w < 1; radius outside 0..8; patch not 8, 16 or 32; a
+ *   cell < 1 or a grid size that is neither h / cell nor ceil(h / cell) (w alike) or < 1; a float pointer not 4-byte
+ *   aligned; with batch > 1 a batch stride smaller than a sample.  AMMC_EUNSUP: h * w > 2^28; batch * tiles >= 2^31.
+ * All decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_fuse_maps_f32(const float* const* src, const int64_t* src_bs, const int32_t* gh, const int32_t* gw, const int32_t* cell,
+                       int32_t n_ch, const float* coef, int32_t batch, int32_t h, int32_t w, int32_t radius, int32_t patch,
+                       float* pixel, int64_t px_bs, float* patch_mean, int64_t pm_bs, float* frame_max, float* workspace,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
