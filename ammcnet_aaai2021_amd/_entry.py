@@ -3,8 +3,9 @@
 warm-up and timed loop, and the fields every entry's JSON line starts with."""
 from __future__ import annotations
 
+import os
 import time
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 import torch
@@ -103,6 +104,43 @@ def load_sources(a, options: str = "--data, --rgb_root/--op_root or --synthetic"
     else:
         raise SystemExit(f"give {options}")
     return sources, gt, streamed
+
+
+RAW_SIZE = (240, 360)        # `synthetic_raw_sources`' camera resolution
+
+
+def masks_from_root(names, mask_root: str):
+    """`names`: the sub-video folder names in evaluation order -> [T, h0, w0] arrays read from mask_root/<name>.npy, None
+    where there is no such file; a .npy file that matches no sub-video raises ValueError"""
+    known = set(names)
+    stray = sorted(f for f in os.listdir(mask_root) if f.endswith(".npy") and f[:-4] not in known)
+    if stray:
+        raise ValueError(f"--mask_root {mask_root}: {stray} match no sub-video folder ({len(known)} folders)")
+    out = []
+    for name in names:
+        path = os.path.join(mask_root, name + ".npy")
+        out.append(np.load(path) if os.path.isfile(path) else None)
+    return out
+
+
+def load_masks(a, sources, blob: dict, synthetic_masks: Callable) -> list:
+    """the pixel ground truth of `load_sources`' sub-videos, one [T, h0, w0] array or None each: the "masks" list of the
+    --data blob, the files of --mask_root, or `synthetic_masks(videos, frames, h, w)` (SystemExit where they are missing,
+    stray, or not one per sub-video)"""
+    if a.data:
+        masks = blob.get("masks")
+        if masks is None:
+            raise SystemExit("--data: the blob has no 'masks' list (one [T,h,w] array or None per sub-video)")
+    elif a.rgb_root and a.op_root:
+        try:
+            masks = masks_from_root(sorted(os.listdir(a.rgb_root)), a.mask_root)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+    else:
+        masks = synthetic_masks(a.videos, a.frames, *(RAW_SIZE if a.raw else (a.size, a.size)))
+    if len(masks) != len(sources):
+        raise SystemExit(f"{len(masks)} masks for {len(sources)} sub-videos")
+    return masks
 
 
 def stager(a, sources, dev, streamed: bool, shard=(0, 1)):

@@ -293,23 +293,33 @@ def assemble_localised(n_frames: int, batches, parts: Sequence[Dict[str, np.ndar
 
 # ---- the pass driver: one sub-video through a pass behind the evaluation forward -------------
 
-class _FlatSlots:
-    """one flat 4-byte device buffer per sub-video carved into named sections (fp32, or int32 for the names in
-    `ints`): batches write straight into their clips' rows and the whole sub-video comes to the host by ONE copy"""
+_SLOT_DTYPES = {torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
 
-    def __init__(self, sections, ints, device):
-        self.layout, self.ints, off = {}, set(ints), 0
-        for name, shape in sections:
-            self.layout[name] = (off, tuple(shape))
-            off += (int(np.prod(shape)) + 3) // 4 * 4                          # sections start 16-byte aligned
-        self.flat = torch.zeros(off, device=device, dtype=torch.float32)
 
-    def view(self, name: str, flat=None):
-        off, shape = self.layout[name]
-        v = (self.flat if flat is None else flat)[off:off + int(np.prod(shape))]
-        if name in self.ints:
-            v = v.view(torch.int32) if isinstance(v, torch.Tensor) else v.view(np.int32)
-        return v.reshape(shape)
+class _Slots:
+    """one flat device buffer of 4-byte words, zeroed, carved into named sections [(name, shape, dtype)] of fp32, int32
+    or uint8, each 16-byte aligned: the launches of a pass write straight into them and everything comes to the host by
+    ONE copy (`flat.cpu().numpy()`, which `view(name, host)` carves the same way).  Words are reinterpreted, never
+    converted: every bit pattern survives."""
+
+    def __init__(self, sections, device):
+        self.layout, off = {}, 0                           # name -> (first word, (shape, dtype))
+        for name, shape, dtype in sections:
+            self.layout[name] = (off, (tuple(shape), dtype))
+            off += (self._words(shape, dtype) + 3) // 4 * 4
+        self.flat = torch.zeros(off, device=device, dtype=torch.int32)
+
+    @staticmethod
+    def _words(shape, dtype) -> int:
+        n = int(np.prod(shape, dtype=np.int64))
+        return (n + 3) // 4 if dtype == torch.uint8 else n
+
+    def view(self, name: str, host: Optional[np.ndarray] = None):
+        off, (shape, dtype) = self.layout[name]
+        v = (self.flat if host is None else host)[off:off + self._words(shape, dtype)]
+        if dtype != torch.int32:
+            v = v.view(dtype if host is None else _SLOT_DTYPES[dtype])
+        return v[:int(np.prod(shape, dtype=np.int64))].reshape(shape)
 
 
 def _checked_batches(who: Optional[str], rgb_frames: torch.Tensor, op_frames: torch.Tensor, batch: int):
@@ -353,17 +363,17 @@ def _run_pass(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, batches,
               predictions: Optional[list] = None, scratch=()) -> Dict[str, np.ndarray]:
     """One sub-video through a pass; the tensors may live on any device.  `sections`: [(name, shape of one clip's row)],
     every name with the prefix of its stream (`rgb_` / `op_`: it picks the clip length of the fills); `ints`: the names
-    that hold int32; `scratch`: names a kernel needs room for but the pass does not return.  The driver carves the
-    sections, and behind them the per-batch commit values and range flags, out of one `_FlatSlots` buffer.  For batch k
-    = clips [s, e) it runs `_forward_batch`, then `on_batch(slots, s, e, k, forward)` under `no_grad`, which writes the
+    that hold int32 (the others fp32); `scratch`: names a kernel needs room for but the pass does not return.  The driver
+    carves the sections, and behind them the per-batch commit values and range flags, out of one `_Slots` buffer.  For
+    batch k = clips [s, e) it runs `_forward_batch`, then `on_batch(slots, s, e, k, forward)` under `no_grad`, which writes the
     pass's outputs into rows [s, e) of its sections (device work only: no wait, no host read).  Every batch is queued
     back to back; ONE device-to-host copy; the batches whose S16 range flag came back set run again with `exact=True`
     (one `_count_fallback` each) and the buffer is copied again.  `predictions` receives (s, e, rgb_pred, op_pred, fused)
     of every batch as scored: a re-run's tuple replaces the plain one.  -> `assemble_localised` over the sections that
     are not scratch, plus `rgb_comm` / `op_comm`."""
     n_clip = batches[-1][1]
-    slots = _FlatSlots([(name, (n_clip,) + tuple(shape)) for name, shape in sections] +
-                       [("comm", (len(batches), 2)), ("flag", (len(batches),))], ints, rgb_frames.device)
+    slots = _Slots([(name, (n_clip,) + tuple(shape), torch.int32 if name in ints else torch.float32) for name, shape in sections] +
+                   [("comm", (len(batches), 2), torch.float32), ("flag", (len(batches),), torch.float32)], rgb_frames.device)
 
     def run(k: int, exact: bool):
         s, e = batches[k]
@@ -1264,6 +1274,67 @@ def pool_mask(mask: torch.Tensor, patch: int) -> torch.Tensor:
 _PIXEL_KEYS = ("m", "kth", "max_in", "max_out")
 
 
+def _checked_mask(who: str, mask: torch.Tensor, t: int, h: int, w: int, dev) -> torch.Tensor:
+    """the ground truth of a mask-aware pass: uint8 (a bool is viewed as uint8: the same memory) [t, h, w] on `dev`,
+    returned contiguous"""
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != dev:
+        raise ValueError(f"{who}: mask must be uint8 {(t, h, w)} on {dev}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    return mask.contiguous()
+
+
+def _frame_mask(who: str, masks, v: int, rgb: torch.Tensor) -> Optional[torch.Tensor]:
+    """masks[v] (a uint8 / bool / numeric [T, h0, w0] array or tensor, or None) on rgb's device at its frame size"""
+    t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
+    if v >= len(masks):
+        raise ValueError(f"{who}: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
+    mk = masks[v]
+    if mk is None:
+        return None
+    mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
+    if mk.dim() != 3 or mk.shape[0] != t:
+        raise ValueError(f"{who}: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
+    if mk.dtype not in (torch.uint8, torch.bool):
+        mk = mk != 0
+    mk = mk.to(rgb.device)
+    return resize_mask(mk.view(torch.uint8) if mk.dtype == torch.bool else mk, (h, w)).contiguous()
+
+
+def _masked_subvideos(who: str, model, videos, masks, out: dict, score: Callable, keep_maps: bool, device=None):
+    """`_scored_subvideos` for the mask-aware loops: `score(v, rgb, op, mask)` receives `_frame_mask` of masks[v] (None
+    for a sub-video without one), `out["mask_videos"]` grows by the sub-videos that have one; yields (v, rec, whether v
+    has a mask, and under `keep_maps` its resized mask on the host - else None)"""
+    held = {}
+
+    def scored(v, rgb, op):
+        held["mask"] = _frame_mask(who, masks, v, rgb)
+        return score(v, rgb, op, held["mask"])
+
+    for v, _, _, rec in _scored_subvideos(model, videos, out, scored, device):
+        has = held["mask"] is not None
+        if has:
+            out["mask_videos"].append(v)
+        yield v, rec, has, held["mask"].cpu().numpy() if has and keep_maps else None
+
+
+def _evaluate_masked(who: str, model, videos, masks, dataset_name: str, keys, subvideo: Callable, keep_maps: bool, device) -> dict:
+    """the loop `evaluate_dataset_pixel` and `evaluate_dataset_region` share: `subvideo(v, rgb, op, mask, keep_maps)` scores
+    one sub-video - one without a mask against a zero mask, for its frame records - and the arrays it returns by `keys`
+    (`mask`: the resized mask) become lists over the sub-videos, None at one without a mask"""
+    out = _new_records(dataset_name, "n_frames", "mask_videos", *keys)
+
+    def score(v, rgb, op, dm):
+        if dm is None:
+            return subvideo(v, rgb, op, torch.zeros((rgb.shape[0],) + tuple(rgb.shape[2:]), device=rgb.device, dtype=torch.uint8), False)
+        return subvideo(v, rgb, op, dm, keep_maps)
+
+    for v, rec, has, host_mask in _masked_subvideos(who, model, videos, masks, out, score, keep_maps, device):
+        for k in keys:
+            out[k].append((host_mask if k == "mask" else rec[k]) if has else None)
+    return out
+
+
 def pixel_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mask: torch.Tensor, patch: int = 16,
                    frac=(2, 5), batch: int = EVAL_BATCH, keep_maps: bool = False) -> Dict[str, np.ndarray]:
     """Is the error where the anomaly is: rgb_frames [T,3,H,W], op_frames [T-1,2,H,W] and mask uint8 (or bool) [T,H,W]
@@ -1282,15 +1353,10 @@ def pixel_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mas
     from . import ops
     batches = _checked_batches("pixel_subvideo", rgb_frames, op_frames, batch)
     t, (h, w) = rgb_frames.shape[0], rgb_frames.shape[2:]
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != rgb_frames.device:
-        raise ValueError(f"pixel_subvideo: mask must be uint8 {(t, h, w)} on {rgb_frames.device}, got {mask.dtype} "
-                         f"{tuple(mask.shape)} on {mask.device}")
-    mask = mask.contiguous()
+    dev = rgb_frames.device
+    mask = _checked_mask("pixel_subvideo", mask, t, h, w, dev)
     pooled = pool_mask(mask, patch)
     ph, pw = pooled.shape[1:]
-    dev = rgb_frames.device
     sections = [(f"rgb_{g}_{key}", ()) for g in ("pix", "patch") for key in _PIXEL_KEYS] + [("rgb_psnr", ()), ("op_psnr", ())]
     if keep_maps:
         sections += [("rgb_pixel_map", (h, w)), ("rgb_patch_map", (ph, pw))]
@@ -1327,33 +1393,8 @@ def evaluate_dataset_pixel(model, videos, masks, dataset_name: str = "synthetic"
     `pixel_subvideo` as lists by their names (`pix_m`, ..., `patch_max_out`; with `keep_maps` `pixel_map`, `patch_map`
     and the resized `mask`), None at a sub-video without a mask."""
     keys = [f"{g}_{key}" for g in ("pix", "patch") for key in _PIXEL_KEYS] + (["pixel_map", "patch_map", "mask"] if keep_maps else [])
-    out = _new_records(dataset_name, "n_frames", "mask_videos", *keys)
-
-    def score(v, rgb, op):
-        t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
-        if v >= len(masks):
-            raise ValueError(f"evaluate_dataset_pixel: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
-        mk = masks[v]
-        if mk is None:
-            dm = torch.zeros((t, h, w), device=rgb.device, dtype=torch.uint8)
-        else:
-            mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
-            if mk.dim() != 3 or mk.shape[0] != t:
-                raise ValueError(f"evaluate_dataset_pixel: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
-            if mk.dtype not in (torch.uint8, torch.bool):
-                mk = mk != 0
-            dm = resize_mask(mk.to(rgb.device).view(torch.uint8) if mk.dtype == torch.bool else mk.to(rgb.device), (h, w)).contiguous()
-        rec = pixel_subvideo(model, rgb, op, dm, patch, frac, keep_maps=keep_maps and mk is not None)
-        if keep_maps and mk is not None:
-            rec["mask"] = dm.cpu().numpy()
-        return rec
-
-    for v, _, _, rec in _scored_subvideos(model, videos, out, score, device):
-        if masks[v] is not None:
-            out["mask_videos"].append(v)
-        for k in keys:
-            out[k].append(rec[k] if masks[v] is not None else None)
-    return out
+    return _evaluate_masked("evaluate_dataset_pixel", model, videos, masks, dataset_name, keys,
+                            lambda v, rgb, op, dm, keep: pixel_subvideo(model, rgb, op, dm, patch, frac, keep_maps=keep), keep_maps, device)
 
 
 def pixel_level_auc(rec: dict, normalise: str = "none") -> dict:
@@ -1497,6 +1538,70 @@ def region_curve_area(fpr, rate) -> float:
     return float(sum((b[0] - a[0]) * (a[1] + b[1]) / 2.0 for a, b in zip(pts, pts[1:])))
 
 
+def _frames_of(a: np.ndarray) -> np.ndarray:
+    """clip rows -> frame rows of the rgb stream, with `assemble_localised`'s head fill"""
+    return np.concatenate([np.repeat(a[:1], RGB_LEN_CLIP - 1, axis=0), a])
+
+
+# The region tail `region_subvideo` and `fused_subvideo` share, over `_Slots` sections: per map g ("pix", "patch") the
+# ground truth - `{g}_gt_count` [n_clip], `{g}_labels` [n_clip, h_g, w_g] - and per scored map `{p}{g}` (p: "" or a
+# setting's prefix) the four figures [n_clip, K] and `{p}{g}_thresholds` [K] as used.
+
+def _region_sections(grids: dict, n_clip: int, K: int, prefixes=("",)) -> list:
+    """`grids`: {g: (h_g, w_g)}"""
+    sections = []
+    for p in prefixes:
+        for g in grids:
+            sections += [(f"{p}{g}_{key}", (n_clip, K), torch.int32) for key in _REGION_KEYS]
+            sections.append((f"{p}{g}_thresholds", (K,), torch.float32))
+    for g, grid in grids.items():
+        sections += [(f"{g}_gt_count", (n_clip,), torch.int32), (f"{g}_labels", (n_clip,) + tuple(grid), torch.uint8)]
+    return sections
+
+
+def _label_truth(slots: _Slots, g: str, mask: torch.Tensor, chunk: int, min_gt_area: int, connectivity: int) -> None:
+    """`ops.label_regions` of the clips' masks [n_clip, h_g, w_g], `chunk` frames at a time"""
+    from . import ops
+    for s in range(0, mask.shape[0], chunk):
+        ops.label_regions(mask[s:s + chunk], min_gt_area, connectivity,
+                          {"labels": slots.view(f"{g}_labels")[s:s + chunk], "count": slots.view(f"{g}_gt_count")[s:s + chunk]})
+
+
+def _score_regions(slots: _Slots, p: str, g: str, mp: torch.Tensor, values: torch.Tensor, t_max, chunk: int, iou, min_area: int,
+                   connectivity: int) -> None:
+    """the thresholds `values` times the largest value of the map `mp` [n_clip, h_g, w_g] (one fp32 multiply on the
+    device) or times `t_max` where given, then `ops.region_scores` against g's label images, `chunk` frames at a time"""
+    from . import ops
+    used = slots.view(f"{p}{g}_thresholds")
+    used.copy_(values * (mp.max() if t_max is None else torch.tensor(float(t_max), device=mp.device, dtype=torch.float32)))
+    for s in range(0, mp.shape[0], chunk):
+        ops.region_scores(mp[s:s + chunk], slots.view(f"{g}_labels")[s:s + chunk], used, iou, min_area, connectivity,
+                          {key: slots.view(f"{p}{g}_{key}")[s:s + chunk] for key in _REGION_KEYS})
+
+
+def _check_regions(who: str, slots: _Slots, host: np.ndarray, prefixes, groups, video: str) -> None:
+    """the counts, once they are on the host: a labelling that hit its round bound (RuntimeError), a frame with more
+    ground-truth regions than are scored (ValueError)"""
+    for g in groups:
+        count = slots.view(f"{g}_gt_count", host)
+        if (count < 0).any() or any((slots.view(f"{p}{g}_n_comp", host) < 0).any() for p in prefixes):
+            raise RuntimeError(f"{who}: the labelling of sub-video {video!r} hit its round bound ({g} map)")
+        if (count > REGION_MAX_REGIONS).any():
+            f = int(np.argmax(count > REGION_MAX_REGIONS))
+            raise ValueError(f"sub-video {video!r}, frame {f + RGB_LEN_CLIP - 1}: {int(count[f])} ground-truth regions on the "
+                             f"{'frame' if g == 'pix' else 'patch grid'}, at most {REGION_MAX_REGIONS} are scored: drop "
+                             f"the specks with --min_gt_area")
+
+
+def _region_arrays(slots: _Slots, host: np.ndarray, p: str, g: str) -> Dict[str, np.ndarray]:
+    """the per-frame arrays of one scored map, by `region_subvideo`'s names"""
+    one = {f"{g}_{key}": _frames_of(slots.view(f"{p}{g}_{key}", host)) for key in _REGION_KEYS}
+    one[f"{g}_gt_count"] = _frames_of(slots.view(f"{g}_gt_count", host))
+    one[f"{g}_labels"] = _frames_of(slots.view(f"{g}_labels", host))
+    one[f"{g}_thresholds"] = slots.view(f"{p}{g}_thresholds", host).copy()
+    return one
+
+
 def region_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mask: torch.Tensor, thresholds, patch: int = 16,
                     iou=(1, 10), min_area: int = 1, connectivity: int = 8, normalise: str = "video", t_max=None,
                     keep_maps: bool = False, min_gt_area: int = 1, batch: int = EVAL_BATCH,
@@ -1522,17 +1627,13 @@ def region_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, ma
         raise ValueError(f"region_subvideo: normalise='none' needs a finite t_max > 0, got {t_max!r}")
     batches = _checked_batches("region_subvideo", rgb_frames, op_frames, batch)
     t, (h, w) = rgb_frames.shape[0], rgb_frames.shape[2:]
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != rgb_frames.device:
-        raise ValueError(f"region_subvideo: mask must be uint8 {(t, h, w)} on {rgb_frames.device}, got {mask.dtype} "
-                         f"{tuple(mask.shape)} on {mask.device}")
     dev, lc, n_clip = rgb_frames.device, RGB_LEN_CLIP, batches[-1][1]
+    mask = _checked_mask("region_subvideo", mask, t, h, w, dev)
     values = torch.as_tensor(np.asarray(thresholds, dtype=np.float32).reshape(-1)).to(dev)
     K = int(values.numel())
     if K < 1:
         raise ValueError("region_subvideo: no thresholds")
-    masks = {"pix": mask.contiguous()[lc - 1:], "patch": pool_mask(mask, patch).contiguous()[lc - 1:]}
+    masks = {"pix": mask[lc - 1:], "patch": pool_mask(mask, patch).contiguous()[lc - 1:]}
     ph, pw = masks["patch"].shape[1:]
     maps = {"pix": torch.empty((n_clip, h, w), device=dev), "patch": torch.empty((n_clip, ph, pw), device=dev)}
     bmax = max(e - s for s, e in batches)
@@ -1548,41 +1649,17 @@ def region_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, ma
 
     rec = _run_pass(model, rgb_frames, op_frames, batches, [("rgb_psnr", ()), ("op_psnr", ())], (), on_batch)
     with torch.no_grad():
-        flat = torch.empty((2, 4 * K + 1, n_clip), device=dev, dtype=torch.int32)      # per map: 4 x [K] rows and the counts, by frame
-        labels, used = {}, {}
-        for gi, g in enumerate(("pix", "patch")):
-            lab = torch.empty_like(masks[g])
-            for s in range(0, n_clip, REGION_FRAME_CHUNK):
-                e = min(s + REGION_FRAME_CHUNK, n_clip)
-                ops.label_regions(masks[g][s:e], min_gt_area, connectivity, {"labels": lab[s:e], "count": flat[gi, 4 * K, s:e]})
-            scale = maps[g].max() if normalise == "video" else torch.tensor(float(t_max), device=dev, dtype=torch.float32)
-            used[g] = values * scale
-            for s in range(0, n_clip, REGION_FRAME_CHUNK):
-                e = min(s + REGION_FRAME_CHUNK, n_clip)
-                res = ops.region_scores(maps[g][s:e], lab[s:e], used[g], iou, min_area, connectivity)
-                for j, key in enumerate(_REGION_KEYS):
-                    flat[gi, j * K:(j + 1) * K, s:e] = res[key].t()
-            labels[g] = lab
-        host = flat.cpu().numpy()                        # the region figures' one copy
-
-    def frames_of(a: np.ndarray) -> np.ndarray:          # clip rows -> frame rows, with `assemble_localised`'s head fill
-        return np.concatenate([np.repeat(a[:1], lc - 1, axis=0), a])
-    for gi, g in enumerate(("pix", "patch")):
-        count = host[gi, 4 * K]
-        if (count < 0).any() or (host[gi, K:2 * K] < 0).any():
-            raise RuntimeError(f"region_subvideo: the labelling of sub-video {video!r} hit its round bound ({g} map)")
-        if (count > REGION_MAX_REGIONS).any():
-            f = int(np.argmax(count > REGION_MAX_REGIONS))
-            raise ValueError(f"sub-video {video!r}, frame {f + lc - 1}: {int(count[f])} ground-truth regions on the "
-                             f"{'frame' if g == 'pix' else 'patch grid'}, at most {REGION_MAX_REGIONS} are scored: drop "
-                             f"the specks with --min_gt_area")
-        for j, key in enumerate(_REGION_KEYS):
-            rec[f"{g}_{key}"] = frames_of(np.ascontiguousarray(host[gi, j * K:(j + 1) * K].T))
-        rec[f"{g}_gt_count"] = frames_of(count.copy())
-        rec[f"{g}_labels"] = frames_of(labels[g].cpu().numpy())
-        rec[f"{g}_thresholds"] = used[g].cpu().numpy()
+        res = _Slots(_region_sections({"pix": (h, w), "patch": (ph, pw)}, n_clip, K), dev)
+        for g in maps:
+            _label_truth(res, g, masks[g], REGION_FRAME_CHUNK, min_gt_area, connectivity)
+            _score_regions(res, "", g, maps[g], values, None if normalise == "video" else t_max, REGION_FRAME_CHUNK, iou, min_area,
+                           connectivity)
+        host = res.flat.cpu().numpy()                    # the region figures' one copy
+    _check_regions("region_subvideo", res, host, ("",), maps, video)
+    for g in maps:
+        rec.update(_region_arrays(res, host, "", g))
     if keep_maps:
-        rec["pixel_map"], rec["patch_map"] = frames_of(maps["pix"].cpu().numpy()), frames_of(maps["patch"].cpu().numpy())
+        rec["pixel_map"], rec["patch_map"] = _frames_of(maps["pix"].cpu().numpy()), _frames_of(maps["patch"].cpu().numpy())
     return rec
 
 
@@ -1601,34 +1678,10 @@ def evaluate_dataset_region(model, videos, masks, dataset_name: str = "synthetic
     a mask."""
     values = region_thresholds(64) if thresholds is None else np.asarray(thresholds, dtype=np.float32)
     keys = list(_REGION_REC_KEYS) + (["pixel_map", "patch_map", "mask"] if keep_maps else [])
-    out = _new_records(dataset_name, "n_frames", "mask_videos", *keys)
-
-    def score(v, rgb, op):
-        t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
-        if v >= len(masks):
-            raise ValueError(f"evaluate_dataset_region: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
-        mk = masks[v]
-        if mk is None:
-            dm = torch.zeros((t, h, w), device=rgb.device, dtype=torch.uint8)
-        else:
-            mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
-            if mk.dim() != 3 or mk.shape[0] != t:
-                raise ValueError(f"evaluate_dataset_region: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
-            if mk.dtype not in (torch.uint8, torch.bool):
-                mk = mk != 0
-            dm = resize_mask(mk.to(rgb.device).view(torch.uint8) if mk.dtype == torch.bool else mk.to(rgb.device), (h, w)).contiguous()
-        rec = region_subvideo(model, rgb, op, dm, values, patch, iou, min_area, connectivity, normalise, t_max,
-                              keep_maps and mk is not None, min_gt_area, video=str(v))
-        if keep_maps and mk is not None:
-            rec["mask"] = dm.cpu().numpy()
-        return rec
-
-    for v, _, _, rec in _scored_subvideos(model, videos, out, score, device):
-        if masks[v] is not None:
-            out["mask_videos"].append(v)
-        for k in keys:
-            out[k].append(rec[k] if masks[v] is not None else None)
-    return out
+    return _evaluate_masked("evaluate_dataset_region", model, videos, masks, dataset_name, keys,
+                            lambda v, rgb, op, dm, keep: region_subvideo(model, rgb, op, dm, values, patch, iou, min_area, connectivity,
+                                                                         normalise, t_max, keep, min_gt_area, video=str(v)),
+                            keep_maps, device)
 
 
 def region_level_auc(rec: dict, alpha=(1, 10)) -> dict:
@@ -1782,29 +1835,6 @@ def fuse_coefficients(weights, maxima=None, normalise: str = "video", scales=Non
     raise ValueError(f"fuse_coefficients: normalise must be 'video' or 'none', got {normalise!r}")
 
 
-class _ByteSlots:
-    """one flat int32 device buffer carved into named sections of int32, fp32 or uint8 (each 16-byte aligned): the scoring
-    launches write straight into them and everything comes to the host by ONE copy"""
-
-    def __init__(self, sections, device):
-        self.layout, off = {}, 0
-        for name, shape, dtype in sections:
-            n = int(np.prod(shape)) if len(shape) else 1
-            words = n if dtype != torch.uint8 else (n + 3) // 4
-            self.layout[name] = (off, tuple(shape), dtype, n)
-            off += (words + 3) // 4 * 4
-        self.flat = torch.zeros(max(off, 4), device=device, dtype=torch.int32)
-
-    def view(self, name: str, host: Optional[np.ndarray] = None):
-        off, shape, dtype, n = self.layout[name]
-        words = n if dtype != torch.uint8 else (n + 3) // 4
-        if host is not None:
-            np_dtype = {torch.int32: np.int32, torch.float32: np.float32, torch.uint8: np.uint8}[dtype]
-            return host[off:off + words].view(np_dtype)[:n].reshape(shape)
-        v = self.flat[off:off + words]
-        return (v if dtype == torch.int32 else v.view(dtype))[:n].reshape(shape)
-
-
 def fused_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mask: Optional[torch.Tensor], weights, radius: int = 2,
                    patch: int = 16, frac=(2, 5), thresholds=None, region: bool = True, normalise: str = "video", scales=None,
                    iou=(1, 10), min_area: int = 1, connectivity: int = 8, t_max=None, keep_maps: bool = False,
@@ -1841,11 +1871,7 @@ def fused_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mas
         raise ValueError(f"fused_subvideo: frames of at least 8 x 8 (the commit maps live on the H/8 x W/8 grid), got {h} x {w}")
     scored = mask is not None
     if scored:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        if mask.dtype != torch.uint8 or tuple(mask.shape) != (t, h, w) or mask.device != dev:
-            raise ValueError(f"fused_subvideo: mask must be uint8 {(t, h, w)} on {dev}, got {mask.dtype} {tuple(mask.shape)} "
-                             f"on {mask.device}")
+        mask = _checked_mask("fused_subvideo", mask, t, h, w, dev)
     values = torch.as_tensor(np.asarray(region_thresholds(64) if thresholds is None else thresholds, dtype=np.float32).reshape(-1)).to(dev)
     K = int(values.numel())
     if region and K < 1:
@@ -1884,105 +1910,57 @@ def fused_subvideo(model, rgb_frames: torch.Tensor, op_frames: torch.Tensor, mas
     if not scored:
         return rec
     names = FUSE_CHANNELS[:n_ch]
-    groups = ("pix", "patch")
-    masks = {"pix": mask.contiguous()[lc - 1:], "patch": pool_mask(mask, patch).contiguous()[lc - 1:]}
-    grid = {"pix": (h, w), "patch": (ph, pw)}
+    masks = {"pix": mask[lc - 1:], "patch": pool_mask(mask, patch).contiguous()[lc - 1:]}
+    grids = {"pix": (h, w), "patch": (ph, pw)}
+    prefixes = [f"{gi}_" for gi in range(G)]
     sections = [("channel_max", (n_ch,), torch.float32), ("coef", (G, n_ch), torch.float32)]
-    for gi in range(G):
-        sections.append((f"{gi}_frame_max", (n_clip,), torch.float32))
-        for g in groups:
-            sections += [(f"{gi}_{g}_{key}", (n_clip,), torch.int32 if key == "m" else torch.float32) for key in _PIXEL_KEYS]
-            if region:
-                sections += [(f"{gi}_{g}_{key}", (n_clip, K), torch.int32) for key in _REGION_KEYS]
-                sections.append((f"{gi}_{g}_thresholds", (K,), torch.float32))
+    for p in prefixes:
+        sections.append((f"{p}frame_max", (n_clip,), torch.float32))
+        sections += [(f"{p}{g}_{key}", (n_clip,), torch.int32 if key == "m" else torch.float32) for g in grids for key in _PIXEL_KEYS]
     if region:
-        for g in groups:
-            sections += [(f"{g}_gt_count", (n_clip,), torch.int32), (f"{g}_labels", (n_clip,) + grid[g], torch.uint8)]
+        sections += _region_sections(grids, n_clip, K, prefixes)
     with torch.no_grad():
-        res = _ByteSlots(sections, dev)
-        fused = {"pix": torch.empty((n_clip, h, w), device=dev), "patch": torch.empty((n_clip, ph, pw), device=dev)}
-        chunks = [(s, min(s + FUSE_FRAME_CHUNK, n_clip)) for s in range(0, n_clip, FUSE_FRAME_CHUNK)]
+        res = _Slots(sections, dev)
+        fused = {g: torch.empty((n_clip,) + grid, device=dev) for g, grid in grids.items()}
         maxima = res.view("channel_max")
         for c, name in enumerate(names):
             maxima[c] = maps[name].amax()
         if region:
-            for g in groups:
-                for s, e in chunks:
-                    ops.label_regions(masks[g][s:e], min_gt_area, connectivity,
-                                      {"labels": res.view(f"{g}_labels")[s:e], "count": res.view(f"{g}_gt_count")[s:e]})
+            for g in grids:
+                _label_truth(res, g, masks[g], FUSE_FRAME_CHUNK, min_gt_area, connectivity)
         kept = []
-        for gi, wv in enumerate(rows):
+        for gi, p in enumerate(prefixes):
             coef = res.view("coef")[gi]
             coef.copy_(fuse_coefficients(wdev[gi], maxima, normalise, sdev))
-            for s, e in chunks:
+            for s in range(0, n_clip, FUSE_FRAME_CHUNK):
+                e = min(s + FUSE_FRAME_CHUNK, n_clip)
                 ops.fuse_maps([maps[name][s:e] for name in names], FUSE_CELLS[:n_ch], coef, radius, patch,
-                              {"pixel": fused["pix"][s:e], "patch_mean": fused["patch"][s:e],
-                               "frame_max": res.view(f"{gi}_frame_max")[s:e]})
-                for g in groups:
-                    ops.pixel_scores(fused[g][s:e], masks[g][s:e], frac,
-                                     {key: res.view(f"{gi}_{g}_{key}")[s:e] for key in _PIXEL_KEYS})
+                              {"pixel": fused["pix"][s:e], "patch_mean": fused["patch"][s:e], "frame_max": res.view(f"{p}frame_max")[s:e]})
+                for g in grids:
+                    ops.pixel_scores(fused[g][s:e], masks[g][s:e], frac, {key: res.view(f"{p}{g}_{key}")[s:e] for key in _PIXEL_KEYS})
             if region:
-                for g in groups:
-                    scale = fused[g].max() if t_max is None else torch.tensor(float(t_max), device=dev, dtype=torch.float32)
-                    used = res.view(f"{gi}_{g}_thresholds")
-                    used.copy_(values * scale)
-                    for s, e in chunks:
-                        ops.region_scores(fused[g][s:e], res.view(f"{g}_labels")[s:e], used, iou, min_area, connectivity,
-                                          {key: res.view(f"{gi}_{g}_{key}")[s:e] for key in _REGION_KEYS})
+                for g in grids:
+                    _score_regions(res, p, g, fused[g], values, t_max, FUSE_FRAME_CHUNK, iou, min_area, connectivity)
             if keep_maps:
                 kept.append((fused["pix"].cpu().numpy(), fused["patch"].cpu().numpy()))
         host = res.flat.cpu().numpy()                    # the fused figures' one copy
-
-    def frames_of(a: np.ndarray) -> np.ndarray:          # clip rows -> frame rows, with `assemble_localised`'s head fill
-        return np.concatenate([np.repeat(a[:1], lc - 1, axis=0), a])
     if region:
-        for g in groups:
-            count = res.view(f"{g}_gt_count", host)
-            if (count < 0).any():
-                raise RuntimeError(f"fused_subvideo: the labelling of sub-video {video!r} hit its round bound ({g} map)")
-            if (count > REGION_MAX_REGIONS).any():
-                f = int(np.argmax(count > REGION_MAX_REGIONS))
-                raise ValueError(f"sub-video {video!r}, frame {f + lc - 1}: {int(count[f])} ground-truth regions on the "
-                                 f"{'frame' if g == 'pix' else 'patch grid'}, at most {REGION_MAX_REGIONS} are scored: drop "
-                                 f"the specks with --min_gt_area")
+        _check_regions("fused_subvideo", res, host, prefixes, grids, video)
     rec["channel_max"], rec["coef"] = res.view("channel_max", host).copy(), res.view("coef", host).copy()
     rec["settings"] = []
-    for gi in range(G):
-        one = {"frame_max": frames_of(res.view(f"{gi}_frame_max", host))}
-        for g in groups:
+    for gi, p in enumerate(prefixes):
+        one = {"frame_max": _frames_of(res.view(f"{p}frame_max", host))}
+        for g in grids:
             for key in _PIXEL_KEYS:
-                one[f"{g}_{key}"] = frames_of(res.view(f"{gi}_{g}_{key}", host))
+                one[f"{g}_{key}"] = _frames_of(res.view(f"{p}{g}_{key}", host))
             if region:
-                if (res.view(f"{gi}_{g}_n_comp", host) < 0).any():
-                    raise RuntimeError(f"fused_subvideo: the labelling of sub-video {video!r} hit its round bound ({g} map)")
-                for key in _REGION_KEYS:
-                    one[f"{g}_{key}"] = frames_of(res.view(f"{gi}_{g}_{key}", host))
-                one[f"{g}_gt_count"] = frames_of(res.view(f"{g}_gt_count", host))
-                one[f"{g}_labels"] = frames_of(res.view(f"{g}_labels", host))
-                one[f"{g}_thresholds"] = res.view(f"{gi}_{g}_thresholds", host).copy()
+                one.update(_region_arrays(res, host, p, g))
         if keep_maps:
-            one["pixel_map"], one["patch_map"] = frames_of(kept[gi][0]), frames_of(kept[gi][1])
+            one["pixel_map"], one["patch_map"] = _frames_of(kept[gi][0]), _frames_of(kept[gi][1])
         rec["settings"].append(one)
     if keep_maps:
-        rec["channel_maps"] = {name: frames_of(maps[name].cpu().numpy()) for name in names}
+        rec["channel_maps"] = {name: _frames_of(maps[name].cpu().numpy()) for name in names}
     return rec
-
-
-def _frame_mask(who: str, masks, v: int, rgb: torch.Tensor) -> Optional[torch.Tensor]:
-    """masks[v] (a uint8 / bool / numeric [T, h0, w0] array or tensor, or None) on rgb's device at its frame size"""
-    t, (h, w) = int(rgb.shape[0]), rgb.shape[2:]
-    if v >= len(masks):
-        raise ValueError(f"{who}: {len(masks)} masks for more than {v} sub-videos (None marks one without)")
-    mk = masks[v]
-    if mk is None:
-        return None
-    mk = torch.as_tensor(np.asarray(mk) if not isinstance(mk, torch.Tensor) else mk)
-    if mk.dim() != 3 or mk.shape[0] != t:
-        raise ValueError(f"{who}: mask {v} is {tuple(mk.shape)}, its sub-video has {t} frames")
-    if mk.dtype not in (torch.uint8, torch.bool):
-        mk = mk != 0
-    mk = mk.to(rgb.device)
-    return resize_mask(mk.view(torch.uint8) if mk.dtype == torch.bool else mk, (h, w)).contiguous()
 
 
 def evaluate_dataset_fused(model, videos, masks, weights, dataset_name: str = "synthetic", radius: int = 2, patch: int = 16,
@@ -2005,18 +1983,12 @@ def evaluate_dataset_fused(model, videos, masks, weights, dataset_name: str = "s
     out = {"weights": rows, "settings": recs, "channel_max": [], "coef": []}
     if keep_maps:
         out["channel_maps"] = []
-    held = {}
 
-    def score(v, rgb, op):
-        held["mask"] = dm = _frame_mask("evaluate_dataset_fused", masks, v, rgb)
+    def score(v, rgb, op, dm):
         return fused_subvideo(model, rgb, op, dm, rows, radius, patch, frac, thresholds, region, normalise, scales, iou, min_area,
                               connectivity, t_max, keep_maps and dm is not None, min_gt_area, video=str(v), budget=budget)
 
-    for v, _, _, rec in _scored_subvideos(model, videos, base, score, device):
-        has = held["mask"] is not None
-        if has:
-            base["mask_videos"].append(v)
-        host_mask = held["mask"].cpu().numpy() if has and keep_maps else None
+    for v, rec, has, host_mask in _masked_subvideos("evaluate_dataset_fused", model, videos, masks, base, score, keep_maps, device):
         for gi, one in enumerate(recs):
             for k in keys:
                 one[k].append((host_mask if k == "mask" else rec["settings"][gi][k]) if has else None)

@@ -10,6 +10,7 @@ parity test (tests/test_gpu_parity.py, tests/test_gpu_s16.py).  No ATen compute 
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -26,6 +27,67 @@ def _need_cuda(x: torch.Tensor):
 
 def _stream(x) -> int:
     return torch.cuda.current_stream(x.device).cuda_stream
+
+
+# ---- what the ops with an `out=` table, a workspace or a (num, den) pair share ----------------
+
+_workspaces: dict = {}       # (name, device index, stream handle) -> the cached workspace
+
+
+def _workspace(name: str, dev: torch.device, n: int, dtype, stream: int) -> torch.Tensor:
+    """at least `n` elements of `dtype` for the op family `name`, cached per (name, device index, stream): launches on
+    one stream run in order, so two calls never use it at once; it only grows"""
+    key = (name, dev.index if dev.index is not None else torch.cuda.current_device(), stream)
+    ws = _workspaces.get(key)
+    if ws is None or ws.numel() < n:
+        _workspaces.pop(key, None)                            # (let the smaller one go before its successor is allocated)
+        ws = _workspaces[key] = torch.empty(n, device=dev, dtype=dtype)
+    return ws
+
+
+def _bs(t: torch.Tensor, n: int) -> int:
+    """the batch stride of [B, ...] with samples of n elements: a dimension of size 1 may carry any stride in torch"""
+    return max(t.stride(0), n) if t.shape[0] == 1 else t.stride(0)
+
+
+def _slots(what: str, out, dev, B: int, want: dict, strided=(), single: bool = False):
+    """The `out=` table of an op.  `want` = {key: (shape, dtype)}, every shape [B, ...]; `out`: the caller's tensors by
+    those keys, or None (`single`: the op's one `out` tensor, which stands for a table of `want`'s one entry).  An unknown
+    key is refused, an absent slot allocated, a given one must be `dtype` `shape` on `dev` and contiguous - or, for the
+    slots `strided` names (those whose batch stride the kernel takes), have contiguous samples and with B > 1 a batch
+    stride of at least the sample's size.
+    -> ({key: tensor} in `want`'s order, {key: batch stride in elements} of the strided slots)"""
+    if single:
+        out = None if out is None else dict.fromkeys(want, out)
+    elif out and not out.keys() <= want.keys():
+        raise ValueError(f"{what}: `out` has no slot {sorted(set(out) - set(want))}")
+    res, bs = {}, {}
+    for key, (shape, dtype) in want.items():
+        t, why = out.get(key) if out else None, None
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dtype)
+        elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            why = f"must be {dtype} {shape} on {dev}"
+        elif not t.is_contiguous() and (key not in strided or not t[0].is_contiguous()
+                                        or (B > 1 and t.stride(0) < math.prod(shape[1:]))):
+            why = "must be contiguous" if key not in strided else "must have contiguous samples and a batch stride >= a sample's size"
+        if why:
+            raise ValueError(f"{what}: {'out' if single else f'out[{key!r}]'} {why}")
+        res[key] = t
+        if key in strided:
+            bs[key] = _bs(t, math.prod(shape[1:]))
+    return res, bs
+
+
+def _pair(what: str, name: str, v, top: int):
+    """(num, den) with 1 <= num <= den <= top"""
+    try:
+        num, den = (int(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be a pair (num, den), got {v!r}") from None
+    if not 1 <= num <= den <= top:
+        raise ValueError(f"{what}: 1 <= num <= den <= {top}, got {v!r}")
+    return num, den
 
 
 def _to_halo(bld: _Builder, x: torch.Tensor, cp: int | None = None, into: Act | None = None) -> Act:
@@ -171,8 +233,8 @@ def error_maps(pred: torch.Tensor, target: torch.Tensor, patch: int = 16, pixel:
     `patch_sum`, `patch_mean` [B, ph, pw], `frame_sq`, `worst` [B], `worst_idx` [B] int32, `pixel` [B, H, W] when asked,
     and `psnr` = 10 log10(C H W / frame_sq) as `EvalEngine.forward` forms it.  Two launches on torch's current stream;
     every sum is taken in a fixed order, so equal inputs give equal bits.  `out`: tensors to write into, by the same
-    keys (views of per-sub-video buffers: a batch then fills its frames' slots) - maps with contiguous rows and
-    columns, any batch stride."""
+    keys (views of per-sub-video buffers: a batch then fills its frames' slots) - a sample's map contiguous, any batch
+    stride of at least its size (samples may not overlap), the [B] slots contiguous."""
     _need_cuda(pred)
     _need_cuda(target)
     if pred.dim() != 4 or pred.shape != target.shape:
@@ -187,34 +249,17 @@ def error_maps(pred: torch.Tensor, target: torch.Tensor, patch: int = 16, pixel:
     B, C, H, W = pred.shape
     ph, pw = (H + patch - 1) // patch, (W + patch - 1) // patch
     dev = pred.device
-    out = dict(out) if out else {}
     want = {"patch_sum": ((B, ph, pw), torch.float32), "patch_mean": ((B, ph, pw), torch.float32),
             "frame_sq": ((B,), torch.float32), "worst": ((B,), torch.float32), "worst_idx": ((B,), torch.int32)}
     if pixel:
         want["pixel"] = ((B, H, W), torch.float32)
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"error_maps: `out` has no slot {sorted(unknown)}")
-    res = {}
-    for key, (shape, dtype) in want.items():
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
-            raise ValueError(f"error_maps: out[{key!r}] must be {dtype} {shape} on {dev}")
-        elif t.dim() == 1 and B > 1 and t.stride(0) != 1:
-            raise ValueError(f"error_maps: out[{key!r}] must be contiguous")
-        elif t.dim() == 3 and not t[0].is_contiguous():
-            raise ValueError(f"error_maps: out[{key!r}]: the map of a sample must be contiguous (any batch stride)")
-        res[key] = t
-    ps, pm = res["patch_sum"], res["patch_mean"]
-    ps_bs = max(ps.stride(0), ph * pw) if B == 1 else ps.stride(0)
-    if B > 1 and pm.stride(0) != ps_bs:
+    res, bs = _slots("error_maps", out, dev, B, want, ("patch_sum", "patch_mean", "pixel"))
+    if B > 1 and bs["patch_mean"] != bs["patch_sum"]:
         raise ValueError("error_maps: out['patch_sum'] and out['patch_mean'] must share one batch stride")
     px = res.get("pixel")
-    px_bs = 0 if px is None else (max(px.stride(0), H * W) if B == 1 else px.stride(0))
     _lib.check(lib.ammc_error_maps_f32(_ptr(pred), *_nchw_strides(pred), _ptr(target), *_nchw_strides(target), B, C, H, W, patch,
-                                       _ptr(ps), ps_bs, _ptr(pm), _ptr(px) if px is not None else None, px_bs,
+                                       _ptr(res["patch_sum"]), bs["patch_sum"], _ptr(res["patch_mean"]),
+                                       _ptr(px) if px is not None else None, bs.get("pixel", 0),
                                        _ptr(res["frame_sq"]), _ptr(res["worst"]), res["worst_idx"].data_ptr(), _stream(pred)),
                "error_maps")
     res["psnr"] = 10.0 * torch.log10(float(C * H * W) / res["frame_sq"])
@@ -224,7 +269,6 @@ def error_maps(pred: torch.Tensor, target: torch.Tensor, patch: int = 16, pixel:
 SSIM_TILE = 32               # tile edge of csrc/ssim.hip (`ammc_ssim_tile()`): where a frame is cut for its fixed-order sums
 SSIM_MAX_CHANNELS = 4
 _ssim_window_c = None
-_ssim_workspaces: dict = {}
 
 
 def ssim_window() -> torch.Tensor:
@@ -233,16 +277,6 @@ def ssim_window() -> torch.Tensor:
     import math
     g = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)], dtype=torch.float32)
     return g / g.sum()
-
-
-def _ssim_workspace(dev: torch.device, stream: int, floats: int) -> torch.Tensor:
-    """the tile partials of `ssim`, cached per (device, stream): launches on one stream run in order, so the next call's
-    first launch cannot overtake this call's second one; it only grows"""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-    ws = _ssim_workspaces.get(key)
-    if ws is None or ws.numel() < floats:
-        ws = _ssim_workspaces[key] = torch.empty(max(floats, 4096), device=dev, dtype=torch.float32)
-    return ws
 
 
 def ssim(pred: torch.Tensor, target: torch.Tensor, map: bool = False, out: dict | None = None) -> dict:
@@ -263,39 +297,20 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, map: bool = False, out: dict 
         raise ValueError("ssim: pixel stride 1 (NCHW views; make channels-last tensors contiguous first)")
     B, C, H, W = pred.shape
     dev = pred.device
-    out = dict(out) if out else {}
-    want = {"ssim": (B,), "ssim_c": (B, C), "sq": (B,)}
+    want = {"ssim": ((B,), torch.float32), "ssim_c": ((B, C), torch.float32), "sq": ((B,), torch.float32)}
     if map:
-        want["map"] = (B, H, W)
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"ssim: `out` has no slot {sorted(unknown)}")
+        want["map"] = ((B, H, W), torch.float32)
+    res, bs = _slots("ssim", out, dev, B, want, ("map",))
     _need_cuda(pred)
     lib = _lib.load()
-    res = {}
-    for key, shape in want.items():
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=torch.float32)
-        elif tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev:
-            raise ValueError(f"ssim: out[{key!r}] must be torch.float32 {shape} on {dev}")
-        elif key == "map":
-            if not t[0].is_contiguous() or (B > 1 and t.stride(0) < H * W):
-                raise ValueError("ssim: out['map']: the map of a sample must be contiguous (any batch stride)")
-        elif not t.is_contiguous():
-            raise ValueError(f"ssim: out[{key!r}] must be contiguous")
-        res[key] = t
     if _ssim_window_c is None:
-        import ctypes
         _ssim_window_c = (ctypes.c_float * 11)(*ssim_window().tolist())
     mp = res.get("map")
-    map_bs = 0 if mp is None else (max(mp.stride(0), H * W) if B == 1 else mp.stride(0))
     stream = _stream(pred)
-    floats = int(lib.ammc_ssim_workspace_floats(B, C, H, W))
-    ws = _ssim_workspace(dev, stream, floats)
+    ws = _workspace("ssim", dev, max(int(lib.ammc_ssim_workspace_floats(B, C, H, W)), 4096), torch.float32, stream)
     _lib.check(lib.ammc_ssim_f32(_ptr(pred), *_nchw_strides(pred), _ptr(target), *_nchw_strides(target), B, C, H, W,
                                  _ssim_window_c, _ptr(res["ssim"]), _ptr(res["ssim_c"]), _ptr(res["sq"]),
-                                 _ptr(mp) if mp is not None else None, map_bs, _ptr(ws), ws.numel(), stream), "ssim")
+                                 _ptr(mp) if mp is not None else None, bs.get("map", 0), _ptr(ws), ws.numel(), stream), "ssim")
     n = float(C * H * W)
     res["mse"] = 256.0 * res["sq"] / n
     res["psnr"] = 10.0 * torch.log10(4.0 * n / res["sq"])
@@ -377,39 +392,18 @@ def pixel_scores(map: torch.Tensor, mask: torch.Tensor, frac=(2, 5), out: dict |
     B, H, W = map.shape
     if B < 1 or H < 1 or W < 1 or H * W > PIXEL_MAX_PIXELS:
         raise ValueError(f"pixel_scores: B, H, W >= 1 and H * W <= {PIXEL_MAX_PIXELS}, got {tuple(map.shape)}")
-    try:
-        num, den = (int(v) for v in frac)
-    except (TypeError, ValueError):
-        raise ValueError(f"pixel_scores: frac must be a pair (num, den), got {frac!r}") from None
-    if not 1 <= num <= den <= PIXEL_MAX_DEN:
-        raise ValueError(f"pixel_scores: 1 <= num <= den <= {PIXEL_MAX_DEN}, got {frac!r}")
+    num, den = _pair("pixel_scores", "frac", frac, PIXEL_MAX_DEN)
     for name, t in (("map", map), ("mask", mask)):
         if not t[0].is_contiguous() or (B > 1 and t.stride(0) < H * W):
             raise ValueError(f"pixel_scores: {name}: a sample must be contiguous, with a batch stride >= H * W")
     if not map.is_cuda or mask.device != map.device:
         raise ValueError("pixel_scores: map and mask must be on one GPU; there is no CPU fallback")
-    dev = map.device
-    out = dict(out) if out else {}
-    want = {"m": torch.int32, "kth": torch.float32, "max_in": torch.float32, "max_out": torch.float32}
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"pixel_scores: `out` has no slot {sorted(unknown)}")
-    res = {}
-    for key, dtype in want.items():
-        t = out.get(key)
-        if t is None:
-            t = torch.empty((B,), device=dev, dtype=dtype)
-        elif tuple(t.shape) != (B,) or t.dtype != dtype or t.device != dev:
-            raise ValueError(f"pixel_scores: out[{key!r}] must be {dtype} {(B,)} on {dev}")
-        elif not t.is_contiguous():
-            raise ValueError(f"pixel_scores: out[{key!r}] must be contiguous")
-        res[key] = t
+    res, _ = _slots("pixel_scores", out, map.device, B, {"m": ((B,), torch.int32), "kth": ((B,), torch.float32),
+                                                         "max_in": ((B,), torch.float32), "max_out": ((B,), torch.float32)})
     lib = _lib.load()
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)                         # a bool is one byte, 0 or 1: the same memory
-    map_bs = max(map.stride(0), H * W) if B == 1 else map.stride(0)
-    mask_bs = max(mask.stride(0), H * W) if B == 1 else mask.stride(0)
-    _lib.check(lib.ammc_pixel_scores_f32(_ptr(map), map_bs, mask.data_ptr(), mask_bs, B, H, W, num, den,
+    _lib.check(lib.ammc_pixel_scores_f32(_ptr(map), _bs(map, H * W), mask.data_ptr(), _bs(mask, H * W), B, H, W, num, den,
                                          res["m"].data_ptr(), _ptr(res["kth"]), _ptr(res["max_in"]), _ptr(res["max_out"]),
                                          _stream(map)), "pixel_scores")
     res["max_all"] = torch.maximum(res["max_in"], res["max_out"])
@@ -423,7 +417,6 @@ REGION_MAX_REGIONS = 32      # ground-truth regions of one frame
 REGION_MAX_DEN = 4096
 REGION_WORKSPACE_BUDGET = 256 << 20   # bytes: `region_scores` splits its thresholds into launches that stay below it
 _REGION_KEYS = ("n_px", "n_comp", "n_fp", "hit")
-_region_ws: dict = {}        # (device, stream) -> the cached workspace
 
 
 def _region_sample_checks(what: str, tensors, min_area, connectivity):
@@ -448,20 +441,6 @@ def _region_sample_checks(what: str, tensors, min_area, connectivity):
     return B, H, W
 
 
-def _region_workspace(dev, nbytes: int) -> torch.Tensor:
-    """cached per (device, stream): launches on one stream run in order, so two calls never use it at once; it only grows"""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _region_ws.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        _region_ws.pop(key, None)
-        ws = _region_ws[key] = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.int32)
-    return ws
-
-
-def _bs(t: torch.Tensor, n: int) -> int:
-    return max(t.stride(0), n) if t.shape[0] == 1 else t.stride(0)
-
-
 def label_regions(mask: torch.Tensor, min_area: int = 1, connectivity: int = 8, out: dict | None = None) -> dict:
     """The ground-truth regions of masks (csrc/region_scores.hip; definitions in include/ammc_hip.h).  `mask` uint8 or
     bool [B, H, W] on the GPU, nonzero = anomalous, contiguous samples with any batch stride >= H * W.  Returns `labels`
@@ -473,28 +452,16 @@ def label_regions(mask: torch.Tensor, min_area: int = 1, connectivity: int = 8, 
     if not mask.is_cuda:
         raise ValueError("label_regions: mask must be on the GPU; there is no CPU fallback")
     dev = mask.device
-    out = dict(out) if out else {}
-    if set(out) - {"labels", "count"}:
-        raise ValueError(f"label_regions: `out` has no slot {sorted(set(out) - {'labels', 'count'})}")
-    labels, count = out.get("labels"), out.get("count")
-    if labels is None:
-        labels = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
-    elif (tuple(labels.shape) != (B, H, W) or labels.dtype != torch.uint8 or labels.device != dev or not labels[0].is_contiguous()
-          or (B > 1 and labels.stride(0) < H * W)):
-        raise ValueError(f"label_regions: out['labels'] must be uint8 {(B, H, W)} on {dev}, samples contiguous")
-    if count is None:
-        count = torch.empty((B,), device=dev, dtype=torch.int32)
-    elif tuple(count.shape) != (B,) or count.dtype != torch.int32 or count.device != dev or not count.is_contiguous():
-        raise ValueError(f"label_regions: out['count'] must be contiguous int32 {(B,)} on {dev}")
+    res, bs = _slots("label_regions", out, dev, B, {"labels": ((B, H, W), torch.uint8), "count": ((B,), torch.int32)}, ("labels",))
     lib = _lib.load()
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
-    need = lib.ammc_region_workspace_bytes(B, 1, H, W)
-    ws = _region_workspace(dev, need)
-    _lib.check(lib.ammc_label_regions_u8(mask.data_ptr(), _bs(mask, H * W), B, H, W, min_area, connectivity, labels.data_ptr(),
-                                         _bs(labels, H * W), count.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(mask)),
+    stream = _stream(mask)
+    ws = _workspace("region", dev, (lib.ammc_region_workspace_bytes(B, 1, H, W) + 3) // 4, torch.int32, stream)
+    _lib.check(lib.ammc_label_regions_u8(mask.data_ptr(), _bs(mask, H * W), B, H, W, min_area, connectivity, res["labels"].data_ptr(),
+                                         bs["labels"], res["count"].data_ptr(), ws.data_ptr(), ws.numel() * 4, stream),
                "label_regions")
-    return {"labels": labels, "count": count}
+    return res
 
 
 def region_scores(map: torch.Tensor, labels: torch.Tensor, thresholds: torch.Tensor, iou=(1, 10), min_area: int = 1,
@@ -516,36 +483,22 @@ def region_scores(map: torch.Tensor, labels: torch.Tensor, thresholds: torch.Ten
         raise ValueError("region_scores: thresholds must be a non-empty fp32 [T] tensor")
     if not thresholds.is_contiguous():
         raise ValueError("region_scores: thresholds must be contiguous")
-    try:
-        num, den = (int(v) for v in iou)
-    except (TypeError, ValueError):
-        raise ValueError(f"region_scores: iou must be a pair (num, den), got {iou!r}") from None
-    if not 1 <= num <= den <= REGION_MAX_DEN:
-        raise ValueError(f"region_scores: 1 <= num <= den <= {REGION_MAX_DEN}, got {iou!r}")
+    num, den = _pair("region_scores", "iou", iou, REGION_MAX_DEN)
     if not map.is_cuda or labels.device != map.device or thresholds.device != map.device:
         raise ValueError("region_scores: map, labels and thresholds must be on one GPU; there is no CPU fallback")
     dev, T = map.device, thresholds.numel()
-    out = dict(out) if out else {}
-    if set(out) - set(_REGION_KEYS):
-        raise ValueError(f"region_scores: `out` has no slot {sorted(set(out) - set(_REGION_KEYS))}")
-    res = {}
-    for key in _REGION_KEYS:
-        t = out.get(key)
-        if t is None:
-            t = torch.empty((B, T), device=dev, dtype=torch.int32)
-        elif tuple(t.shape) != (B, T) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"region_scores: out[{key!r}] must be contiguous int32 {(B, T)} on {dev}")
-        res[key] = t
+    res, _ = _slots("region_scores", out, dev, B, {key: ((B, T), torch.int32) for key in _REGION_KEYS})
     lib = _lib.load()
     per_t = lib.ammc_region_workspace_bytes(B, 1, H, W)
     chunk = max(1, min(T, REGION_WORKSPACE_BUDGET // per_t))
-    ws = _region_workspace(dev, per_t * chunk)
+    stream = _stream(map)
+    ws = _workspace("region", dev, (per_t * chunk + 3) // 4, torch.int32, stream)
     for t0 in range(0, T, chunk):
         tc = min(chunk, T - t0)
         _lib.check(lib.ammc_region_scores_f32(_ptr(map), _bs(map, H * W), labels.data_ptr(), _bs(labels, H * W), B, H, W,
                                               _ptr(thresholds[t0:]), tc, num, den, min_area, connectivity,
                                               *(res[key][:, t0:].data_ptr() for key in _REGION_KEYS), T, ws.data_ptr(),
-                                              ws.numel() * 4, _stream(map)), "region_scores")
+                                              ws.numel() * 4, stream), "region_scores")
     return res
 
 
@@ -555,8 +508,6 @@ FUSE_MAX_CHANNELS = 4
 FUSE_MAX_RADIUS = 8
 FUSE_MAX_PIXELS = 1 << 28    # h * w of one sample
 FUSE_TILE = (32, 64)         # the tile of csrc/fuse_maps.hip: the workspace holds one float per tile and sample
-_FUSE_KEYS = ("pixel", "patch_mean", "frame_max")
-_fuse_ws: dict = {}          # (device, stream) -> the cached workspace
 
 
 def fuse_maps(sources, cells, coef: torch.Tensor, radius: int = 0, patch: int = 16, out: dict | None = None) -> dict:
@@ -611,39 +562,21 @@ def fuse_maps(sources, cells, coef: torch.Tensor, radius: int = 0, patch: int = 
     if coef.device != dev or any(s.device != dev for s in sources):
         raise ValueError("fuse_maps: the sources and coef must be on one device")
     ph, pw = (H + patch - 1) // patch, (W + patch - 1) // patch
-    want = {"pixel": (B, H, W), "patch_mean": (B, ph, pw), "frame_max": (B,)}
-    out = dict(out) if out else {}
-    if set(out) - set(want):
-        raise ValueError(f"fuse_maps: `out` has no slot {sorted(set(out) - set(want))}")
-    res = {}
-    for key, shape in want.items():
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=torch.float32)
-        elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev:
-            raise ValueError(f"fuse_maps: out[{key!r}] must be fp32 {shape} on {dev}")
-        elif t.dim() == 1 and not t.is_contiguous():
-            raise ValueError(f"fuse_maps: out[{key!r}] must be contiguous")
-        elif t.dim() == 3 and (not t[0].is_contiguous() or (B > 1 and t.stride(0) < shape[1] * shape[2])):
-            raise ValueError(f"fuse_maps: out[{key!r}]: the map of a sample must be contiguous, with a batch stride >= its size")
-        res[key] = t
+    res, bs = _slots("fuse_maps", out, dev, B, {"pixel": ((B, H, W), torch.float32), "patch_mean": ((B, ph, pw), torch.float32),
+                                                "frame_max": ((B,), torch.float32)}, ("pixel", "patch_mean"))
     if dev.type != "cuda":
         raise ValueError("fuse_maps: the sources and coef must be on the GPU; there is no CPU fallback")
     lib = _lib.load()
-    tiles = B * (-(-H // FUSE_TILE[0])) * (-(-W // FUSE_TILE[1]))
-    wkey = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _fuse_ws.get(wkey)                                   # launches on one stream run in order; it only grows
-    if ws is None or ws.numel() < tiles:
-        ws = _fuse_ws[wkey] = torch.empty(tiles, device=dev, dtype=torch.float32)
+    stream = _stream(sources[0])
+    ws = _workspace("fuse", dev, B * (-(-H // FUSE_TILE[0])) * (-(-W // FUSE_TILE[1])), torch.float32, stream)
     ptrs = (ctypes.c_void_p * n_ch)(*(s.data_ptr() for s in sources))
     strides = (ctypes.c_int64 * n_ch)(*(_bs(s, s.shape[1] * s.shape[2]) for s in sources))
     ghs = (ctypes.c_int32 * n_ch)(*(s.shape[1] for s in sources))
     gws = (ctypes.c_int32 * n_ch)(*(s.shape[2] for s in sources))
     cls = (ctypes.c_int32 * n_ch)(*cells)
-    px, pm = res["pixel"], res["patch_mean"]
     _lib.check(lib.ammc_fuse_maps_f32(ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(ghs), ctypes.addressof(gws), ctypes.addressof(cls),
-                                      n_ch, _ptr(coef), B, H, W, radius, patch, _ptr(px), _bs(px, H * W), _ptr(pm), _bs(pm, ph * pw),
-                                      _ptr(res["frame_max"]), _ptr(ws), _stream(sources[0])), "fuse_maps")
+                                      n_ch, _ptr(coef), B, H, W, radius, patch, _ptr(res["pixel"]), bs["pixel"], _ptr(res["patch_mean"]),
+                                      bs["patch_mean"], _ptr(res["frame_max"]), _ptr(ws), stream), "fuse_maps")
     return res
 
 
@@ -667,7 +600,7 @@ def _render_input(what: str, name: str, t, c: int, like=None) -> int:
                          f"{tuple(like.shape)} on {like.device}")
     if not t[0].is_contiguous() or (B > 1 and t.stride(0) < c * H * W):
         raise ValueError(f"{what}: {name}: a sample must be contiguous, with a batch stride >= C * H * W")
-    return max(t.stride(0), c * H * W) if B == 1 else t.stride(0)
+    return _bs(t, c * H * W)
 
 
 def _render_vector(what: str, name: str, v, B: int, dev) -> torch.Tensor:
@@ -688,15 +621,8 @@ def _render_scale(what: str, scale):
 
 def _render_out(what: str, out, shape, dev) -> tuple:
     """the uint8 [B, h, w, 3] output (allocated when None) and its batch stride in bytes"""
-    B = shape[0]
-    per = shape[1] * shape[2] * 3
-    if out is None:
-        out = torch.empty(shape, device=dev, dtype=torch.uint8)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != dev:
-        raise ValueError(f"{what}: out must be torch.uint8 {tuple(shape)} on {dev}")
-    elif not out[0].is_contiguous() or (B > 1 and out.stride(0) < per):
-        raise ValueError(f"{what}: out: a sample's picture must be contiguous, with a batch stride >= its size")
-    return out, (max(out.stride(0), per) if B == 1 else out.stride(0))
+    res, bs = _slots(what, out, dev, shape[0], {"out": (shape, torch.uint8)}, ("out",), single=True)
+    return res["out"], bs["out"]
 
 
 def flow_to_rgb(flow: torch.Tensor, scale=(1.0, 1.0), max_rad: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -747,11 +673,7 @@ def render_stats(rgb_pred: torch.Tensor, rgb_target: torch.Tensor, op_pred: torc
     su, sv = _render_scale(what, flow_scale)
     B, _, H, W = rgb_pred.shape
     dev = rgb_pred.device
-    if out is None:
-        out = torch.empty((B, 4), device=dev, dtype=torch.float32)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, 4) or out.device != dev \
-            or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be contiguous torch.float32 {(B, 4)} on {dev}")
+    out = _slots(what, out, dev, B, {"out": ((B, 4), torch.float32)}, single=True)[0]["out"]
     _render_need_gpu(what, rgb_pred)
     lib = _lib.load()
     _lib.check(lib.ammc_render_stats_f32(_ptr(rgb_pred), strides[0], _ptr(rgb_target), strides[1], _ptr(op_pred), strides[2],
@@ -809,7 +731,6 @@ def render_panels(rgb_pred: torch.Tensor, rgb_target: torch.Tensor, op_pred: tor
     out, out_bs = _render_out(what, out, (B, len(rows) * H, len(rows[0]) * W, 3), dev)
     _render_need_gpu(what, rgb_pred)
     lib = _lib.load()
-    import ctypes
     need = (max_rad is None and (3 in ids or 4 in ids)) or (heat_rgb is None and 2 in ids) or (heat_op is None and 5 in ids)
     stream = _stream(rgb_pred)
     ptrs = [_ptr(rgb_pred), strides[0], _ptr(rgb_target), strides[1], _ptr(op_pred), strides[2], _ptr(op_target), strides[3]]
@@ -868,32 +789,14 @@ def memory_scores(quan, x: torch.Tensor, indices: bool = False, out: dict | None
         xv = xv.contiguous()                                  # the one copy: NCHW-contiguous input -> channels last
     enc_w, enc_b, embed = enc_w.float().contiguous(), enc_b.float().contiguous(), embed.float().contiguous()
     e_md, enorm = _Packer(dev).codebook(embed)
-    out = dict(out) if out else {}
     want = {"map": ((B, h, w), torch.float32), "commit": ((B,), torch.float32), "worst": ((B,), torch.float32),
             "worst_idx": ((B,), torch.int32)}
     if indices:
         want["idx"] = ((B, h, w, k), torch.int32)
-    unknown = set(out) - set(want)
-    if unknown:
-        raise ValueError(f"memory_scores: `out` has no slot {sorted(unknown)}")
-    res = {}
-    for key, (shape, dtype) in want.items():
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
-            raise ValueError(f"memory_scores: out[{key!r}] must be {dtype} {shape} on {dev}")
-        elif key == "map":
-            if not t[0].is_contiguous() or (B > 1 and t.stride(0) < h * w):
-                raise ValueError("memory_scores: out['map']: the map of a clip must be contiguous (any batch stride)")
-        elif not t.is_contiguous():
-            raise ValueError(f"memory_scores: out[{key!r}] must be contiguous")
-        res[key] = t
-    mp = res["map"]
-    map_bs = max(mp.stride(0), h * w) if B == 1 else mp.stride(0)
+    res, bs = _slots("memory_scores", out, dev, B, want, ("map",))
     idx = res.get("idx")
     _lib.check(lib.ammc_memory_scores_f32(_ptr(xv), *_nhwc_strides(xv), B, h, w, c, _ptr(enc_w), _ptr(enc_b), _ptr(embed),
-                                          _ptr(e_md), _ptr(enorm), d, m, k, _ptr(mp), map_bs,
+                                          _ptr(e_md), _ptr(enorm), d, m, k, _ptr(res["map"]), bs["map"],
                                           idx.data_ptr() if idx is not None else None, _ptr(res["commit"]), _ptr(res["worst"]),
                                           res["worst_idx"].data_ptr(), _stream(x)), "memory_scores")
     return res

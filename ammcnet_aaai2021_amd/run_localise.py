@@ -19,12 +19,10 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
 
 import numpy as np
 
 from . import _entry, harness
-from .run_pixel import RAW_SIZE, masks_from_root
 from .run_region import _pair, synthetic_region_masks
 
 FIGURES = ("auc_pixel", "auc_pixel_patch", "auc_frame_max", "pointing", "rbdc", "tbdc", "rbdc_patch", "tbdc_patch")
@@ -94,19 +92,7 @@ def main(argv=None):
         raise SystemExit("--rgb_root / --op_root need --mask_root DIR for the pixel ground truth")
     blob: dict = {}
     sources, gt, streamed = _entry.load_sources(a, blob=blob)
-    if a.data:
-        masks = blob.get("masks")
-        if masks is None:
-            raise SystemExit("--data: the blob has no 'masks' list (one [T,h,w] array or None per sub-video)")
-    elif a.rgb_root and a.op_root:
-        try:
-            masks = masks_from_root(sorted(os.listdir(a.rgb_root)), a.mask_root)
-        except ValueError as e:
-            raise SystemExit(str(e)) from None
-    else:
-        masks = synthetic_region_masks(a.videos, a.frames, *(RAW_SIZE if a.raw else (a.size, a.size)))
-    if len(masks) != len(sources):
-        raise SystemExit(f"{len(masks)} masks for {len(sources)} sub-videos")
+    masks = _entry.load_masks(a, sources, blob, synthetic_region_masks)
 
     def loop(srcs, mks):
         st = _entry.stager(a, srcs, dev, streamed)

@@ -18,13 +18,12 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
 
 import numpy as np
 
 from . import _entry, harness, synthetic
 
-RAW_SIZE = (240, 360)        # `run_test.synthetic_raw_sources`' camera resolution
+masks_from_root = _entry.masks_from_root
 
 
 def synthetic_masks(n_videos: int, frames: int, h: int, w: int):
@@ -40,20 +39,6 @@ def synthetic_masks(n_videos: int, frames: int, h: int, w: int):
             y0, x0 = int(u[f, 3] * (h - rh + 1)), int(u[f, 4] * (w - rw + 1))
             mk[f, y0:min(y0 + rh, h), x0:min(x0 + rw, w)] = 1
         out.append(mk)
-    return out
-
-
-def masks_from_root(names, mask_root: str):
-    """`names`: the sub-video folder names in evaluation order -> [T, h0, w0] arrays read from mask_root/<name>.npy, None
-    where there is no such file; a .npy file that matches no sub-video raises ValueError"""
-    known = set(names)
-    stray = sorted(f for f in os.listdir(mask_root) if f.endswith(".npy") and f[:-4] not in known)
-    if stray:
-        raise ValueError(f"--mask_root {mask_root}: {stray} match no sub-video folder ({len(known)} folders)")
-    out = []
-    for name in names:
-        path = os.path.join(mask_root, name + ".npy")
-        out.append(np.load(path) if os.path.isfile(path) else None)
     return out
 
 
@@ -79,19 +64,7 @@ def main(argv=None):
         raise SystemExit("--rgb_root / --op_root need --mask_root DIR for the pixel ground truth")
     blob: dict = {}
     sources, gt, streamed = _entry.load_sources(a, blob=blob)
-    if a.data:
-        masks = blob.get("masks")
-        if masks is None:
-            raise SystemExit("--data: the blob has no 'masks' list (one [T,h,w] array or None per sub-video)")
-    elif a.rgb_root and a.op_root:
-        try:
-            masks = masks_from_root(sorted(os.listdir(a.rgb_root)), a.mask_root)
-        except ValueError as e:
-            raise SystemExit(str(e)) from None
-    else:
-        masks = synthetic_masks(a.videos, a.frames, *(RAW_SIZE if a.raw else (a.size, a.size)))
-    if len(masks) != len(sources):
-        raise SystemExit(f"{len(masks)} masks for {len(sources)} sub-videos")
+    masks = _entry.load_masks(a, sources, blob, synthetic_masks)
 
     def loop(srcs, mks):
         st = _entry.stager(a, srcs, dev, streamed)

@@ -150,6 +150,47 @@ def test_ceil_grids_and_a_zero_coefficient():
     assert _same(_bits(zero), _bits(one))
 
 
+def test_a_workspace_per_stream_one_for_cuda_and_cuda0_and_no_overlapping_out_samples():
+    """`ops._workspace` under `fuse_maps`, `label_regions` and `region_scores`: two streams, two
+    buffers each; tensors made under torch.device("cuda") and under "cuda:0" on one stream share one; the results are those
+    of the default stream.  And the rule `error_maps` gained: `out` samples that overlap are refused."""
+    B, h, w = 2, 17, 23
+    g = torch.Generator().manual_seed(23)
+    maps, mask = torch.rand((B, h, w), generator=g), torch.rand((B, h, w), generator=g) > 0.7
+    values = torch.tensor([0.25, 0.5, 0.75])
+    rkeys = ("n_px", "n_comp", "n_fp", "hit")
+
+    def run(dev):
+        mp = maps.to(dev)
+        fused = ops.fuse_maps([mp], (1,), torch.ones(1, device=dev), 1, 8)
+        labels = ops.label_regions(mask.to(dev))["labels"]
+        scores = ops.region_scores(fused["pixel"], labels, values.to(dev))
+        return [fused[k] for k in KEYS] + [labels] + [scores[k] for k in rkeys]
+    base = run(DEV)
+    s1, s2 = torch.cuda.Stream(DEV), torch.cuda.Stream(DEV)
+    torch.cuda.synchronize()
+    idx = torch.device(DEV).index
+    got, used = [], []
+    for stream, dev in ((s1, DEV), (s2, torch.device("cuda")), (s1, torch.device("cuda")), (s2, DEV)):
+        with torch.cuda.stream(stream):
+            got.append(run(dev))
+        used.append([ops._workspaces[(name, idx, stream.cuda_stream)].data_ptr() for name in ("fuse", "region")])
+    torch.cuda.synchronize()
+    assert int(base[-4].sum()) > 0 and int(base[3].max()) > 0                 # something was scored against some region
+    for res in got:
+        assert all(torch.equal(a, b) for a, b in zip(res, base))
+    assert used[0] == used[2] and used[1] == used[3]                           # "cuda" and "cuda:0" on one stream: one workspace
+    assert all(a != b for a, b in zip(used[0], used[1]))                       # two streams: two
+    assert {k[1] for k in ops._workspaces} == {idx}                            # keyed by the device's index, never by its spelling
+    pred, target = torch.rand((B, 3, h, w), generator=g).to(DEV), torch.rand((B, 3, h, w), generator=g).to(DEV)
+    overlapping = torch.empty(h * w + 10, device=DEV).as_strided((B, h, w), (10, w, 1))
+    with pytest.raises(ValueError, match="batch stride"):
+        ops.error_maps(pred, target, 8, True, {"pixel": overlapping})
+    apart = torch.empty(2 * h * w + 10, device=DEV).as_strided((B, h, w), (h * w + 10, w, 1))
+    want = ops.error_maps(pred, target, 8, True)
+    assert torch.equal(ops.error_maps(pred, target, 8, True, {"pixel": apart})["pixel"], want["pixel"])
+
+
 # ---- the pass ----------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

@@ -207,7 +207,7 @@ def test_two_streams_each_with_its_own_workspace():
     for g in got_b:
         _equal(base_b, g)
     idx = torch.device(DEV).index
-    w1, w2 = ops._ssim_workspaces[(idx, s1.cuda_stream)], ops._ssim_workspaces[(idx, s2.cuda_stream)]
+    w1, w2 = ops._workspaces[("ssim", idx, s1.cuda_stream)], ops._workspaces[("ssim", idx, s2.cuda_stream)]
     assert w1.data_ptr() != w2.data_ptr()
 
 
