@@ -183,6 +183,9 @@ SIGNATURES = {
     "ammc_ssim_f32": (C.c_int, [_p] + _s3 + [_p] + _s3 + [_i32] * 4 + [_p, _p, _p, _p, _p, _i64, _p, _i64, _p]),
     "ammc_fusion_sweep_max_sorted": (C.c_int, []),
     "ammc_fusion_sweep_f32": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p]),
+    "ammc_curve_sweep_max_class": (C.c_int, []),
+    "ammc_curve_sweep_workspace_bytes": (C.c_int64, [_i32, _i32, _i32]),
+    "ammc_curve_sweep_f32": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _i64, _p]),
     "ammc_pixel_scores_f32": (C.c_int, [_p, _i64, _p, _i64] + [_i32] * 5 + [_p, _p, _p, _p, _p]),
     "ammc_render_stats_f32": (C.c_int, [_p, _i64] * 4 + [_i32] * 3 + [_f32, _f32, _p, _p]),
     "ammc_render_panels_u8": (C.c_int, [_p, _i64] * 4 + [_i32] * 3 + [_f32, _f32, _p, _i32, _i32, _p, _i32, _p, _p, _p, _f32,

@@ -28,19 +28,15 @@
 // of the CU's 160 at mpad = 32768 = ammc_fusion_sweep_max_sorted().  256 threads up to mpad = 4096, 1024 above.
 // Frame indices are clamped to [0, n): a list that is not a partition of 0..n-1 gives a meaningless count, never an
 // access outside chan.  Contraction into FMAs is off for the whole file: every product and sum above is rounded.
-#include "ammc_common.h"
-
-#pragma clang fp contract(off)
+#include "sweep_keys.h"                                // fs_key, fs_bitonic_sort; contraction off for the whole file
 
 namespace ammc_impl {
 
-constexpr int FS_MAX_K = 8;
 constexpr int FS_MAX_SORTED = 32768;
 constexpr int FS_THREADS_SMALL = 256;
 constexpr int FS_THREADS_LARGE = 1024;
 constexpr int FS_SMALL_PAD = 4096;                     // mpad up to which a workgroup has FS_THREADS_SMALL threads
 constexpr int FS_MAX_WAVES = FS_THREADS_LARGE / AMMC_WAVE;
-constexpr unsigned FS_SENTINEL = 0xFFFFFFFFu;
 
 struct FsArgs {
   const float* chan;
@@ -53,25 +49,6 @@ struct FsArgs {
   int k, n, s, m, mpad, r;
   int sorted_is_neg;
 };
-
-// the order-preserving key of frame i at one grid point
-__device__ __forceinline__ unsigned fs_key(const float* __restrict__ chan, int64_t rs, int k, int n, const float (&w)[FS_MAX_K],
-                                           float a, float b, int i) {
-  i = i < 0 ? 0 : (i >= n ? n - 1 : i);
-  const int h = i > 0 ? i - 1 : 0;
-  float f = w[0] * chan[i], fh = w[0] * chan[h];
-#pragma unroll
-  for (int c = 1; c < FS_MAX_K; ++c) {
-    if (c < k) {
-      const float* __restrict__ row = chan + (int64_t)c * rs;
-      f = f + w[c] * row[i];
-      fh = fh + w[c] * row[h];
-    }
-  }
-  const float t = i > 0 ? a * fh + b * f : f;
-  const unsigned u = __float_as_uint(t + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fs_smem[];
 
@@ -88,23 +65,7 @@ __global__ __launch_bounds__(FS_THREADS_LARGE) void fusion_sweep_kernel(FsArgs p
     keys[j] = j < p.m ? fs_key(p.chan, p.rs, p.k, p.n, w, a, b, p.sorted_idx[j]) : FS_SENTINEL;
   __syncthreads();
 
-  // ascending bitonic network over mpad words
-  const int half = p.mpad >> 1;
-  for (int k2 = 2; k2 <= p.mpad; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < half; t += nt) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int hi = lo | j;
-        const unsigned x = keys[lo], y = keys[hi];
-        const bool up = (lo & k2) == 0;
-        if ((x > y) == up) {
-          keys[lo] = y;
-          keys[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  fs_bitonic_sort(keys, p.mpad, tid, nt);
 
   long long acc = 0;
   for (int e = tid; e < p.r; e += nt) {

@@ -1227,6 +1227,132 @@ def sweep_fusion(records: dict, gt: Sequence[np.ndarray], channels: Sequence[str
     return out
 
 
+# ---- curve sweep: EER, average precision and precision-recall area over the same grid ----
+# The reference's other two evaluation types (`compute_eer`, `precision_recall_auc`: main/eval_metric.py:442-446) from a
+# device pass of its own (`ops.curve_sweep`); `sweep_fusion` above is untouched.
+
+def roc_eer(labels: np.ndarray, scores: np.ndarray, pos_label: int = 0, drop_intermediate: bool = True) -> float:
+    """`cal_eer(*roc_curve(labels, scores, pos_label))` (main/eval_metric.py:315-318) restated: the false-positive rate at
+    the vertex where |fpr + tpr - 1| is smallest, the first one on a tie.  The vertices are sklearn's: one per distinct
+    score, of which `drop_intermediate` keeps those where the second difference of the false- or of the true-positive
+    count is non-zero, and both ends; then the origin in front.  The rates are the float64 quotients sklearn forms."""
+    y = np.asarray(labels) == pos_label
+    s = np.asarray(scores)
+    order = np.argsort(s, kind="mergesort")[::-1]
+    y, s = y[order], s[order]
+    idx = np.r_[np.where(np.diff(s))[0], y.size - 1]
+    tps = np.cumsum(y)[idx]
+    fps = 1 + idx - tps
+    if drop_intermediate and len(fps) > 2:
+        keep = np.r_[True, np.logical_or(np.diff(fps, 2), np.diff(tps, 2)), True]
+        fps, tps = fps[keep], tps[keep]
+    tps, fps = np.r_[0, tps], np.r_[0, fps]
+    fpr, tpr = fps / fps[-1], tps / tps[-1]
+    return float(fpr[np.nanargmin(np.absolute(fpr + tpr - 1))])
+
+
+def fused_keys(chan: np.ndarray, w, pair) -> np.ndarray:
+    """key[i] of one grid point on the host, as include/ammc_hip.h defines it: every product and sum one rounded fp32
+    numpy operation, left to right; `pair` = (a, b)"""
+    chan, w = np.asarray(chan, dtype=np.float32), np.asarray(w, dtype=np.float32)
+    f = w[0] * chan[0]
+    for k in range(1, chan.shape[0]):
+        f = f + w[k] * chan[k]
+    t = f.copy()
+    t[1:] = np.float32(pair[0]) * f[:-1] + np.float32(pair[1]) * f[1:]
+    return t + np.float32(0.0)
+
+
+CURVE_KEYS = ("auc", "eer", "eer_vertex", "ap", "pr_auc")
+
+
+def curve_metrics(two_u, pts, thr, sums, n_pos: int, n_neg: int) -> dict:
+    """what include/ammc_hip.h derives from `ops.curve_sweep`'s outputs, in float64 and any leading shape: `auc`, `eer`
+    (the crossing of segment a-b with fpr + tpr = 1), `eer_vertex` (`cal_eer` on the full curve), `ap`, `pr_auc`, and
+    `threshold_eer`: the key value of `eer_vertex`'s vertex (a frame is called positive iff its key >= it)"""
+    pts = np.asarray(pts, dtype=np.int64)
+    P, Q = np.int64(n_pos), np.int64(n_neg)
+    tpa, fpa, tpb, fpb = (pts[..., i] for i in range(4))
+    ga, gb = P * fpa + Q * tpa - P * Q, P * fpb + Q * tpb - P * Q
+    first = np.abs(ga) <= np.abs(gb)
+    lam = -ga / (gb - ga).astype(np.float64)
+    sums, thr = np.asarray(sums, dtype=np.float64), np.asarray(thr)
+    return {"auc": np.asarray(two_u) / (2.0 * float(P) * float(Q)), "eer": (fpa + lam * (fpb - fpa)) / float(Q),
+            "eer_vertex": np.where(first, fpa, fpb) / float(Q), "ap": sums[..., 0] / float(P), "pr_auc": sums[..., 1] / float(P),
+            "threshold_eer": np.where(first, thr[..., 0], thr[..., 1])}
+
+
+def sweep_curves(records: dict, gt: Sequence[np.ndarray], channels: Sequence[str] = ("rgb_img_pred", "rgb_fea_comm"),
+                 weights=None, smooth: Optional[Sequence[float]] = None, positive: str = "normal", device=None) -> dict:
+    """AUC, equal error rate, average precision and precision-recall area of the fused score at every point of a grid
+    (`ops.curve_sweep`); inputs as `sweep_fusion` takes them.  `positive`: "normal" (the reference's pos_label = 0) or
+    "anomalous" - what a detection paper's AP means: the two classes change places and the weights their sign, which
+    negates every key exactly.  Returns float64 [G, S] arrays `auc`, `eer`, `eer_vertex`, `ap`, `pr_auc`, `threshold_eer`
+    (`curve_metrics`), the device's `pts` and `two_u`, `n_pos`, `n_neg`, `weights` (as given, before the sign),
+    `lam_smooth`, `sweep_ms` (the launches of the grid between device events) and `best` = {"auc": argmax, "eer": argmin of
+    `eer`, "ap": argmax}, each {weights, lam_smooth, index, the five values, threshold_eer, eer_reference} - on equal values
+    the first in grid order.  `eer_reference` is the reference's literal call, `roc_eer` with sklearn's default vertex
+    dropping, on the host.  For two channels of a dataset in LAM_MAP, `at_lam_map` holds the same at the published pair.
+    The HIP pass is the only implementation: a GPU is required."""
+    from . import ops
+    if positive not in ("normal", "anomalous"):
+        raise ValueError(f"sweep_curves: positive must be 'normal' or 'anomalous', got {positive!r}")
+    channels = tuple(channels)
+    chan = fusion_channels(records, channels)
+    labels = np.concatenate([np.asarray(g)[DECIDABLE_IDX:] for g in gt])
+    K, N = chan.shape
+    if labels.shape[0] != N:
+        raise ValueError(f"sweep_curves: {labels.shape[0]} labels for {N} scored frames")
+    if not np.isfinite(chan).all():
+        bad = [c for c, row in zip(channels, chan) if not np.isfinite(row).all()]
+        raise ValueError(f"sweep_curves: non-finite normalised scores in {bad} (a constant record, or a NaN / inf in it)")
+    is_pos = (labels == 0) if positive == "normal" else (labels != 0)
+    pos, neg = np.flatnonzero(is_pos), np.flatnonzero(~is_pos)
+    if pos.size == 0 or neg.size == 0:
+        raise ValueError("sweep_curves: the labels hold one class only: the curves are undefined")
+    sign = np.float32(1.0 if positive == "normal" else -1.0)
+    grid = fusion_grid(K)
+    w = grid["weights"] if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1, K))
+    lam_smooth = list(grid["lam_smooth"] if smooth is None else smooth)
+    sm = smoothing_pairs(lam_smooth)
+    lam = LAM_MAP.get(records.get("dataset")) if K == 2 else None
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(dev)
+    d_chan, d_pos, d_neg = up(chan, torch.float32), up(pos, torch.int32), up(neg, torch.int32)
+    with torch.cuda.device(dev):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        d_w, d_sm = up(sign * w, torch.float32), up(sm, torch.float32)
+        t0.record()
+        d_grid = ops.curve_sweep(d_chan, d_pos, d_neg, d_w, d_sm)
+        t1.record()
+        if lam is not None:                               # one more grid point of a second, 1 x 1 launch
+            w_lam, sm_lam = np.array([[1 - lam[0], lam[0]]], dtype=np.float32), smoothing_pairs([lam[1]])
+            d_lam = ops.curve_sweep(d_chan, d_pos, d_neg, up(sign * w_lam, torch.float32), up(sm_lam, torch.float32))
+        res = {k: v.cpu().numpy() for k, v in d_grid.items()}
+        ms = t0.elapsed_time(t1)
+    P, Q = int(pos.size), int(neg.size)
+    m = curve_metrics(res["two_u"], res["pts"], res["thr"], res["sums"], P, Q)
+
+    def point(values, at, wv, pair, l2):
+        out = {"weights": [float(x) for x in wv], "lam_smooth": float(l2)}
+        out.update({k: float(values[k][at]) for k in CURVE_KEYS + ("threshold_eer",)})
+        out["eer_reference"] = roc_eer(is_pos, fused_keys(chan, sign * np.asarray(wv, dtype=np.float32), pair), pos_label=True)
+        return out
+    best = {}
+    for name, flat in (("auc", np.argmax(m["auc"])), ("eer", np.argmin(m["eer"])), ("ap", np.argmax(m["ap"]))):
+        gi, si = (int(x) for x in np.unravel_index(int(flat), m["auc"].shape))
+        best[name] = dict(point(m, (gi, si), w[gi], sm[si], lam_smooth[si]), index=(gi, si))
+    out = dict(m, two_u=res["two_u"], pts=res["pts"], n_pos=P, n_neg=Q, channels=channels, positive=positive, weights=w,
+               lam_smooth=lam_smooth, sweep_ms=float(ms), best=best)
+    if lam is not None:
+        r = {k: v.cpu().numpy() for k, v in d_lam.items()}
+        out["at_lam_map"] = point(curve_metrics(r["two_u"], r["pts"], r["thr"], r["sums"], P, Q), (0, 0), w_lam[0], sm_lam[0], lam[1])
+        out["lam_map"] = tuple(lam)
+    return out
+
+
 # ---- pixel-level evaluation: mask-aware frame scores from the error maps (DESIGN.md section 5.21) ----
 # A pass of its own behind the evaluation forward and `ops.error_maps` (`ops.pixel_scores`, csrc/pixel_scores.hip): nothing
 # above is touched.  The pixel-level criterion (Mahadevan et al.) at the fraction num / den: a frame with ground-truth

@@ -323,6 +323,31 @@ FUSION_MAX_CHANNELS = 8
 FUSION_MAX_SORTED = 32768    # `ammc_fusion_sweep_max_sorted()`: the smaller class is sorted in one workgroup's LDS
 
 
+def _sweep_args(what: str, chan, pos_idx, neg_idx, weights, smooth):
+    """the argument checks the two sweeps share -> (K, N, P, Q, G, S, row stride of chan)"""
+    if chan.dim() != 2 or chan.dtype != torch.float32:
+        raise ValueError(f"{what}: chan must be fp32 [K, N], got {chan.dtype} {tuple(chan.shape)}")
+    K, N = chan.shape
+    if not 1 <= K <= FUSION_MAX_CHANNELS or N < 2:
+        raise ValueError(f"{what}: 1 <= K <= {FUSION_MAX_CHANNELS} channels over N >= 2 frames, got K = {K}, N = {N}")
+    if chan.stride(1) != 1 or (K > 1 and chan.stride(0) < N):
+        raise ValueError(f"{what}: chan needs frame stride 1 and a row stride >= N")
+    dev = chan.device
+    for name, t in (("pos_idx", pos_idx), ("neg_idx", neg_idx)):
+        if t.dim() != 1 or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous int32 vector on {dev}")
+    P, Q = pos_idx.numel(), neg_idx.numel()
+    if P < 1 or Q < 1 or P + Q != N:
+        raise ValueError(f"{what}: both classes non-empty and P + Q == N, got P = {P}, Q = {Q}, N = {N}")
+    if weights.dim() != 2 or weights.shape[1] != K or weights.shape[0] < 1 or smooth.dim() != 2 or smooth.shape[1] != 2 \
+            or smooth.shape[0] < 1:
+        raise ValueError(f"{what}: weights [G, {K}] and smooth [S, 2], got {tuple(weights.shape)} and {tuple(smooth.shape)}")
+    for name, t in (("weights", weights), ("smooth", smooth)):
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous fp32 on {dev}")
+    return K, N, P, Q, weights.shape[0], smooth.shape[0], chan.stride(0) if K > 1 else max(chan.stride(0), N)
+
+
 def fusion_sweep(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tensor, weights: torch.Tensor,
                  smooth: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """Twice the Mann-Whitney U statistic - the exact numerator of the frame-level AUC - of the fused, smoothed score at
@@ -333,40 +358,60 @@ def fusion_sweep(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tenso
     `weights` fp32 [G, K], `smooth` fp32 [S, 2] (the pairs (a, b)), both on the GPU.  Returns int64 [G, S] (`out`, when
     given: contiguous int64 [G, S]); AUC = two_u / (2 P Q).  One launch on torch's current stream; an integer sum, so
     the same values on every launch.  The smaller class may have at most FUSION_MAX_SORTED frames: ValueError beyond."""
-    if chan.dim() != 2 or chan.dtype != torch.float32:
-        raise ValueError(f"fusion_sweep: chan must be fp32 [K, N], got {chan.dtype} {tuple(chan.shape)}")
-    K, N = chan.shape
-    if not 1 <= K <= FUSION_MAX_CHANNELS or N < 2:
-        raise ValueError(f"fusion_sweep: 1 <= K <= {FUSION_MAX_CHANNELS} channels over N >= 2 frames, got K = {K}, N = {N}")
-    if chan.stride(1) != 1 or (K > 1 and chan.stride(0) < N):
-        raise ValueError("fusion_sweep: chan needs frame stride 1 and a row stride >= N")
+    K, N, P, Q, G, S, rs = _sweep_args("fusion_sweep", chan, pos_idx, neg_idx, weights, smooth)
     dev = chan.device
-    for name, t in (("pos_idx", pos_idx), ("neg_idx", neg_idx)):
-        if t.dim() != 1 or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"fusion_sweep: {name} must be a contiguous int32 vector on {dev}")
-    P, Q = pos_idx.numel(), neg_idx.numel()
-    if P < 1 or Q < 1 or P + Q != N:
-        raise ValueError(f"fusion_sweep: both classes non-empty and P + Q == N, got P = {P}, Q = {Q}, N = {N}")
-    if weights.dim() != 2 or weights.shape[1] != K or weights.shape[0] < 1 or smooth.dim() != 2 or smooth.shape[1] != 2 \
-            or smooth.shape[0] < 1:
-        raise ValueError(f"fusion_sweep: weights [G, {K}] and smooth [S, 2], got {tuple(weights.shape)} and {tuple(smooth.shape)}")
-    for name, t in (("weights", weights), ("smooth", smooth)):
-        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"fusion_sweep: {name} must be contiguous fp32 on {dev}")
     if min(P, Q) > FUSION_MAX_SORTED:
         raise ValueError(f"fusion_sweep: the smaller class has {min(P, Q)} frames, the pass sorts at most "
                          f"{FUSION_MAX_SORTED} (ammc_fusion_sweep_max_sorted) in a workgroup's LDS")
-    G, S = weights.shape[0], smooth.shape[0]
     _need_cuda(chan)
     if out is None:
         out = torch.empty((G, S), device=dev, dtype=torch.int64)
     elif tuple(out.shape) != (G, S) or out.dtype != torch.int64 or out.device != dev or not out.is_contiguous():
         raise ValueError(f"fusion_sweep: out must be contiguous torch.int64 {(G, S)} on {dev}")
     lib = _lib.load()
-    rs = chan.stride(0) if K > 1 else max(chan.stride(0), N)
     _lib.check(lib.ammc_fusion_sweep_f32(_ptr(chan), rs, K, N, _ptr(weights), G, _ptr(smooth), S, _ptr(pos_idx), P,
                                          _ptr(neg_idx), Q, _ptr(out), _stream(chan)), "fusion_sweep")
     return out
+
+
+# ---- curve sweep: EER bracket, average precision and PR area (csrc/curve_sweep.hip) ------------
+
+CURVE_MAX_CLASS = 32768      # `ammc_curve_sweep_max_class()`: both classes are sorted in one workgroup's LDS, one after the other
+
+
+def curve_sweep(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tensor, weights: torch.Tensor, smooth: torch.Tensor,
+                max_workspace_bytes: int = 64 << 20, out: dict | None = None) -> dict:
+    """At every point of a grid: `two_u` int64 [G, S] (`fusion_sweep`'s, bit for bit), `pts` int32 [G, S, 4] - the two ROC
+    vertices (TP_a, FP_a, TP_b, FP_b) that bracket fpr + tpr = 1 -, `thr` fp32 [G, S, 2], their thresholds, and `sums`
+    fp64 [G, S, 2], P times the average precision and P times the precision-recall area (csrc/curve_sweep.hip; the
+    definitions and what the caller derives from them are in include/ammc_hip.h).  Inputs as `fusion_sweep` takes them.
+    Each grid point needs a row of max(P, Q) words of workspace: the grid is launched in chunks of points whose rows fit
+    `max_workspace_bytes`, on torch's current stream; the values do not depend on the chunking.  `out`: a dict of any of
+    the four tensors, contiguous.  Either class may have at most CURVE_MAX_CLASS frames: ValueError beyond."""
+    K, N, P, Q, G, S, rs = _sweep_args("curve_sweep", chan, pos_idx, neg_idx, weights, smooth)
+    dev = chan.device
+    if max(P, Q) > CURVE_MAX_CLASS:
+        raise ValueError(f"curve_sweep: the larger class has {max(P, Q)} frames, the pass sorts at most "
+                         f"{CURVE_MAX_CLASS} (ammc_curve_sweep_max_class) in a workgroup's LDS")
+    lib = _lib.load()
+    row = lib.ammc_curve_sweep_workspace_bytes(1, P, Q)
+    if max_workspace_bytes < row:
+        raise ValueError(f"curve_sweep: max_workspace_bytes = {max_workspace_bytes} is below one grid point's row of {row} bytes")
+    _need_cuda(chan)
+    res, _ = _slots("curve_sweep", out, dev, G, {"two_u": ((G, S), torch.int64), "pts": ((G, S, 4), torch.int32),
+                                                 "thr": ((G, S, 2), torch.float32), "sums": ((G, S, 2), torch.float64)})
+    fit = max_workspace_bytes // row                          # grid points per launch: whole weight rows, or parts of one
+    chunks = [(g0, min(g0 + fit // S, G), 0, S) for g0 in range(0, G, fit // S)] if fit >= S else \
+        [(g0, g0 + 1, s0, min(s0 + fit, S)) for g0 in range(G) for s0 in range(0, S, fit)]
+    stream = _stream(chan)
+    ws = _workspace("curve_sweep", dev, max((g1 - g0) * (s1 - s0) for g0, g1, s0, s1 in chunks) * row, torch.uint8, stream)
+    for g0, g1, s0, s1 in chunks:
+        at = g0 * S + s0
+        _lib.check(lib.ammc_curve_sweep_f32(
+            _ptr(chan), rs, K, N, _ptr(weights[g0:g1]), g1 - g0, _ptr(smooth[s0:s1]), s1 - s0, _ptr(pos_idx), P, _ptr(neg_idx), Q,
+            _ptr(res["two_u"].view(-1)[at:]), _ptr(res["pts"].view(-1, 4)[at:]), _ptr(res["thr"].view(-1, 2)[at:]),
+            _ptr(res["sums"].view(-1, 2)[at:]), _ptr(ws), ws.numel(), stream), "curve_sweep")
+    return res
 
 
 # ---- pixel-level evaluation (csrc/pixel_scores.hip) -------------------------------------------

@@ -5,6 +5,11 @@ records come from an evaluation run here (`run_quality`'s model and data options
 and MSE) or from a file written by `--save_records`.  Labels are required.  One JSON line: "channels", "grid" [G, S],
 "n_pos", "n_neg", "sweep_ms" (the launch between device events), "best" {weights, lam_smooth, auc, index}, "auc_best"
 and - for two channels - "auc_at_lam_map", for the default channels `fuse_scores_auc`'s AUC.  One GPU.
+`--curves` adds a second device pass and, to the line, "eer_best", "ap_best", "pr_auc_best" (the
+grid's lowest equal error rate, highest average precision and the precision-recall area beside it) and - for two channels
+- "eer_at_lam_map" (on the full ROC curve, interpolated), "eer_vertex_at_lam_map" (at a vertex), "eer_reference_at_lam_map"
+(the reference's literal `compute_eer`), "pr_auc_at_lam_map" and "threshold_eer_at_lam_map"; `--positive anomalous` scores
+the anomalous class as the positive one.
 
     python -m ammcnet_aaai2021_amd.run_fusion --synthetic [--save_records REC.npz] [--out GRID.npz]
     python -m ammcnet_aaai2021_amd.run_fusion --records REC.npz --channels rgb_img_pred,rgb_ssim,rgb_fea_comm,op_fea_comm
@@ -12,6 +17,7 @@ and - for two channels - "auc_at_lam_map", for the default channels `fuse_scores
 """
 from __future__ import annotations
 
+import argparse
 import json
 
 import numpy as np
@@ -30,7 +36,23 @@ def build_parser():
     p.add_argument("--step", type=float, default=None,
                    help="weight step of the grid (default: the reference's 100 x 20 grid for two channels, 0.1 otherwise)")
     p.add_argument("--out", default=None, help="write auc, two_u, weights and smooth to this .npz")
+    p.epilog = "curve options (a parser of their own, so that the namespace above is what it was):\n" + curves_parser().format_help()
+    p.formatter_class = argparse.RawDescriptionHelpFormatter
     return p
+
+
+def curves_parser():
+    p = argparse.ArgumentParser(add_help=False, usage=argparse.SUPPRESS, allow_abbrev=False)
+    p.add_argument("--curves", action="store_true",
+                   help="also sweep the equal error rate, the average precision and the precision-recall area (their arrays join --out)")
+    p.add_argument("--positive", choices=("normal", "anomalous"), default="normal", help="the positive class of --curves")
+    return p
+
+
+def parse_args(argv=None):
+    """(the entry's namespace, exactly what `build_parser` gave before the curve options existed; theirs)"""
+    a, rest = build_parser().parse_known_args(argv)
+    return a, curves_parser().parse_args(rest)
 
 
 def flatten_records(rec: dict, gt) -> dict:
@@ -64,7 +86,7 @@ def evaluate(a, dev):
 
 
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    a, cv = parse_args(argv)
     if a.maps_dir or a.ssim_maps:
         raise SystemExit("run_fusion writes no maps: --maps_dir / --ssim_maps belong to run_quality")
     channels = tuple(c.strip() for c in a.channels.split(",") if c.strip())
@@ -81,9 +103,19 @@ def main(argv=None):
            "n_neg": res["n_neg"], "sweep_ms": round(res["sweep_ms"], 4), "best": res["best"], "auc_best": res["best"]["auc"]}
     if "auc_at_lam_map" in res:
         out["auc_at_lam_map"], out["lam_map"] = res["auc_at_lam_map"], list(res["lam_map"])
+    arrays = {}
+    if cv.curves:
+        cur = harness.sweep_curves(rec, gt, channels, weights=weights, positive=cv.positive, device=dev)
+        out.update(positive=cv.positive, curves_ms=round(cur["sweep_ms"], 4), eer_best=cur["best"]["eer"]["eer"],
+                   ap_best=cur["best"]["ap"]["ap"], pr_auc_best=cur["best"]["ap"]["pr_auc"],
+                   best_curves={k: v for k, v in cur["best"].items() if k != "auc"})
+        if "at_lam_map" in cur:
+            out.update({f"{k}_at_lam_map": cur["at_lam_map"][k] for k in ("eer", "eer_vertex", "eer_reference", "pr_auc", "ap",
+                                                                          "threshold_eer")})
+        arrays = {k: cur[k] for k in ("eer", "eer_vertex", "ap", "pr_auc", "threshold_eer", "pts")}
     if a.out:
         np.savez(a.out, auc=res["auc"], two_u=res["two_u"], weights=res["weights"],
-                 smooth=harness.smoothing_pairs(res["lam_smooth"]))
+                 smooth=harness.smoothing_pairs(res["lam_smooth"]), **arrays)
         out["out"] = a.out
     print(json.dumps(out))
 

@@ -842,6 +842,52 @@ int ammc_fusion_sweep_f32(const float* chan, int64_t chan_rs, int32_t k, int32_t
                           int64_t* two_u, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Curve sweep (csrc/curve_sweep.hip): at every point of the same grid, what the equal error rate, the average precision
+ * and the precision-recall area of the fused score are made of (the reference's other two evaluation types, `compute_eer`
+ * and `precision_recall_auc`, main/eval_metric.py:442-446), from a pass of its own.
+ * chan, chan_rs, k, n, w, g, sm, s, pos_idx, n_pos, neg_idx, n_neg and key[i] are exactly those of ammc_fusion_sweep_f32:
+ * rounded fp32, left to right, nothing contracted, key = t + 0.0f.  The positive class is the NORMAL one (the reference's
+ * pos_label = 0).  Per grid point, with P = n_pos, Q = n_neg, and for a value v
+ *   TP(v)   = the number of positives with key >= v,  FP(v)   = the number of negatives with key >= v
+ *   TPgt(v) = the number of positives with key >  v,  FPgt(v) = the number of negatives with key >  v
+ * let v_1 > ... > v_D be the distinct values of all n keys.  Vertex d of the ROC curve is (TP(v_d), FP(v_d)), vertex 0 is
+ * (0, 0) with the threshold +inf, and G_d = P * FP_d + Q * TP_d - P * Q in int64 (P Q (fpr + tpr - 1)) rises strictly
+ * from -P Q to +P Q.  With a the largest d with G_d <= 0 and b = a + 1:
+ *   two_u   int64 [g][s]     ammc_fusion_sweep_f32's, bit for bit
+ *   pts     int32 [g][s][4]  (TP_a, FP_a, TP_b, FP_b)
+ *   thr     fp32  [g][s][2]  (v_a, v_b), the key values themselves; v_a = +inf when a = 0
+ *   sums    fp64  [g][s][2]  over the distinct key values u of the positives, with m(u) = TP(u) - TPgt(u):
+ *             sums[0] = sum of m(u) * TP(u) / (TP(u) + FP(u))
+ *             sums[1] = sum of 0.5 * m(u) * (L(u) + TP(u) / (TP(u) + FP(u))),  L(u) = TPgt(u) / (TPgt(u) + FPgt(u)) if
+ *                       TPgt(u) > 0, else 0 if FPgt(u) > 0, else 1 (the curve's appended point: recall 0, precision 1)
+ * From these the caller derives, in double:
+ *   eer_vertex = FP_a / Q if |G_a| <= |G_b| else FP_b / Q      the reference's `cal_eer` (fpr at argmin |fnr - fpr|, the
+ *                first index on a tie) on the FULL curve, sklearn's roc_curve(drop_intermediate=False)
+ *   eer        = (FP_a + lam * (FP_b - FP_a)) / Q, lam = -G_a / (G_b - G_a): where segment a-b crosses fpr + tpr = 1
+ *   ap         = sums[0] / P     sklearn's average_precision_score
+ *   pr_auc     = sums[1] / P     the reference's auc(recall, precision) over precision_recall_curve
+ * The integers and thr are exact.  Each sum has at most P terms, a term at most its m(u), so any order of evaluation is
+ * within (P + 4) * 2^-53 of the real value after the division by P; the order here is fixed by n_pos and n_neg alone, so
+ * all outputs are the same on every launch: a point alone or inside a grid, from any chan_rs, on any stream.
+ * One launch, one workgroup per grid point: the larger class's keys are sorted in LDS and written to the point's row of
+ * `workspace`, the smaller class's are sorted in the same LDS, and each sorted array is walked once, its tie runs counted
+ * by position and the other class's counts found by binary search.  No float atomics, no arrival counter, nothing passes
+ * between workgroups.  `workspace`: DEVICE memory of at least ammc_curve_sweep_workspace_bytes(g * s, n_pos, n_neg) bytes
+ * (g * s rows of max(n_pos, n_neg) words, a row rounded up to 64 words; 0 for a non-positive argument or a class over the
+ * capacity), scratch of this launch alone.
+ * Capacity: max(n_pos, n_neg) <= ammc_curve_sweep_max_class() = 32768 (128 KiB of the CU's 160 KiB of LDS).
+ * AMMC_EINVAL: everything ammc_fusion_sweep_f32 refuses but its capacity; a class over this capacity; a null output or
+ * workspace; pts, thr or workspace not 4-byte aligned, two_u or sums not 8-byte aligned; workspace_bytes below the
+ * query's answer for g * s points.  AMMC_EUNSUP: g * s >= 2^31.  All of them are decided before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ammc_curve_sweep_max_class(void);
+int64_t ammc_curve_sweep_workspace_bytes(int32_t points, int32_t n_pos, int32_t n_neg);
+int ammc_curve_sweep_f32(const float* chan, int64_t chan_rs, int32_t k, int32_t n, const float* w, int32_t g, const float* sm,
+                         int32_t s, const int32_t* pos_idx, int32_t n_pos, const int32_t* neg_idx, int32_t n_neg,
+                         int64_t* two_u, int32_t* pts, float* thr, double* sums, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pixel-level evaluation (csrc/pixel_scores.hip): what the pixel-level criterion of Mahadevan et al. needs of a score
  * map and a ground-truth mask, per sample, from a pass of its own.
  *   map      fp32 [batch][h][w], higher = more anomalous; a sample contiguous (h * w floats), samples map_bs floats apart
