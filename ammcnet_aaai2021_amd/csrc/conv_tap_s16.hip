@@ -1060,9 +1060,8 @@ static int launch_tap(const TapArgs& a, hipStream_t stream, char* label, int lab
   constexpr int NB = KH ? 2 : (NT == 256 && (BN == 128 || BN == 32)) ? 2 : 3;
   constexpr int A_FLOATS = KH ? 2 * ((T_HP * 64 + 768) / 4) + 256 : AS * T_ASTAGE;       // as in conv_tap_s16_tile
   constexpr int STAGES = A_FLOATS + NB * BJ * (NT / 8) * 32 + 256;      // + 1 KB: scale / shift of the tile's filters
-  static const size_t pad = getenv("AMMC_TAP_LDSPAD") ? (size_t)atoi(getenv("AMMC_TAP_LDSPAD")) : 0;   // occupancy experiments
-  const size_t lds = (size_t)STAGES * sizeof(float) + pad;
-  static_assert((size_t)STAGES * sizeof(float) <= 160 * 1024, "LDS budget");
+  constexpr size_t lds = (size_t)STAGES * sizeof(float);
+  static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = conv_tap_s16_kernel<WGM, WGN, TM, TN, AS, MF, KH>;
   if constexpr (KH != 0 && MF == 0) {
     if (a.d.bn_c) kern = conv_tap_s16_kernel<WGM, WGN, TM, TN, AS, MF, KH, true>;

@@ -234,9 +234,10 @@ __global__ __launch_bounds__(WS_NT, 2) void wgrad_s16_kernel(WgradS16Args a) {
   }
 }
 
-// wgrad_tap_s16.hip: the halo-patch form; -12345 = not its case
+// wgrad_tap3_s16.hip: the halo-patch form; -12345 = not its case (`slabs`, `query`: its slab entry's, not used here)
 // `label` non-null: nothing is launched, the kernel's name goes to label[0..label_len) (ammc_conv_wgrad_s16_variant)
-int wgrad_tap_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, char* label, int label_len);
+int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, float* slabs, int query,
+                       char* label, int label_len);
 
 }  // namespace ammc_s16
 using namespace ammc_s16;
@@ -302,8 +303,8 @@ static int wgrad_s16_dispatch(const AmmcWgradDesc* desc, const float* g_inv_scal
   WgradS16Args a;
   const int rc = wgrad_s16_prepare(desc, g_inv_scale, true, a);
   if (rc != AMMC_OK) return rc;
-  if (a.d.ntaps == 9 && a.a_step == 1) {                    // the halo-patch forms: stride-1 3x3 layers
-    const int rt = wgrad_tap_s16_try(a.d, g_inv_scale, a.kpad, (hipStream_t)stream, label, label_len);
+  if (a.d.ntaps == 9 && a.a_step == 1) {                    // the halo-patch form: stride-1 3x3 layers
+    const int rt = wgrad_tap3_s16_try(a.d, g_inv_scale, a.kpad, (hipStream_t)stream, nullptr, 0, label, label_len);
     if (rt != -12345) return rt;
   }
   if (label) {
@@ -323,8 +324,8 @@ extern "C" int ammc_conv_wgrad_s16_variant(const AmmcWgradDesc* desc, char* out,
   return wgrad_s16_dispatch(desc, nullptr, nullptr, out, out_len);
 }
 
-// The deterministic form: wgrad_s16_kernel for EVERY descriptor the checks accept (the halo-patch dispatchers and their
-// switches are not asked), slabs + the fixed-order reduce.
+// The deterministic form: wgrad_s16_kernel for EVERY descriptor the checks accept (the halo-patch dispatcher and its
+// switch are not asked), slabs + the fixed-order reduce.
 extern "C" int64_t ammc_conv_wgrad_s16_det_floats(const AmmcWgradDesc* desc) {
   WgradS16Args a;
   if (wgrad_s16_prepare(desc, nullptr, false, a) != AMMC_OK || a.msplit <= 1) return 0;   // refused, or one split: stored straight into dw

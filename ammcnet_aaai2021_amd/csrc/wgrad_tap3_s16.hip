@@ -1,8 +1,8 @@
-// 3x3 weight gradient, S16 operands, halo patch in LDS (see wgrad_tap_s16.hip), with THREE MFMAs per product block.
+// 3x3 weight gradient, S16 operands, halo patch in LDS, with THREE MFMAs per product block.
 //
-// wgrad_tap_s16.hip feeds an MFMA 16 channels x {hi, lo} per operand: one instruction yields the four plane products
-// of a 16 x 16 channel block, of which lo*lo is wasted, and an accumulator tile covers only 16 x 16 outputs - nine taps
-// x 144 registers hold 16 x 16 x 9 outputs per wave, 20 transposed LDS reads feed 9 MFMAs.
+// The form before it (retired) fed an MFMA 16 channels x {hi, lo} per operand: one instruction yields the
+// four plane products of a 16 x 16 channel block, of which lo*lo is wasted, and an accumulator tile covers only 16 x 16
+// outputs - nine taps x 144 registers hold 16 x 16 x 9 outputs per wave, 20 transposed LDS reads feed 9 MFMAs.
 //
 // Here an MFMA row is ONE plane of a channel and the planes are concatenated along K (K = pixels; the 16 K slots of
 // an MFMA are two lane halves of 8):
@@ -30,7 +30,7 @@
 // Variants <NG, NA, NP, PH> (32-channel blocks of the gradient / of the input, row groups, patch rows):
 //   <4, 2, 1, 2> 128 x 64 channel tiles (N % 128 == 0)          <2, 2, 2, 2> 64 x 64, the two patch rows on different waves
 //   <1, 2, 4, 4> 32 gradient channels (the output layer)        <2, 1, 4, 4> Cin <= 32 (first layers, zero-padded block)
-// Needs W % 32 == 0, H % 2 == 0 (% 4 for the 4-row patches); wgrad_tap_s16_try falls back otherwise.
+// Needs W % 32 == 0, H % 2 == 0 (% 4 for the 4-row patches); wgrad_s16_dispatch falls back to wgrad_s16_kernel otherwise.
 //
 // ROLL (round 5, the two-row patches): a workgroup walks DOWN a 32-pixel column of the image and keeps the input halo
 // rows in a ring of four two-row groups - patch ty reads rows 2 ty - 1 .. 2 ty + 2 = groups ty and ty + 1, and while it is
@@ -100,17 +100,13 @@ __device__ __forceinline__ f16x8u w3_frag(u32x2u a, u32x2u b) {
 // patch (waves of different groups add their parts to the same outputs).  PH = 4 with one row per wave serves the thin
 // operands: 32 gradient channels (the output layer) or 16 / 8 input channels (the first layers; channels beyond Cin
 // are read from the caller's zero buffer).
-// GW = 2 (round 4, four waves, ONE per SIMD with the whole 512-register file): a wave owns TWO 32-channel blocks of the
-// gradient, so a transposed A fragment - four of the 4.7 LDS reads a step costs - feeds six MFMAs instead of three:
-// 0.9 reads per MFMA instead of 1.4 (the kernel runs at 0.52 of the matrix pipe with its LDS reads at ~80 % of the MFMA
-// time).  288 accumulator registers per lane; the same 128 x 64 channel workgroup tile as <4, 2, 1, 2>.
-template <int NG, int NA, int NP, int PH, int GW = 1, int ROLL = 0, int G11 = 0>
-__global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_tap3_s16_kernel(WgradTap3Args a) {
-  static_assert((NG * NA * NP == 8 || (GW == 2 && NG * NA * NP == 4)) && (PH == 2 || PH == 4) && PH % NP == 0, "8 (4) waves");
+template <int NG, int NA, int NP, int PH, int ROLL = 0, int G11 = 0>
+__global__ __launch_bounds__(64 * NG * NA * NP, 2) void wgrad_tap3_s16_kernel(WgradTap3Args a) {
+  static_assert(NG * NA * NP == 8 && (PH == 2 || PH == 4) && PH % NP == 0, "8 waves");
   static_assert(!ROLL || PH == 2, "the ring holds two-row groups");
   constexpr int W3_NT = 64 * NG * NA * NP;
   constexpr int W3_PH = PH, W3_PX = PH * W3_PW, W3_HPX = (PH + 2) * W3_HW, RPW = PH / NP;
-  constexpr int W3_TN = 32 * NG * GW, W3_TC = 32 * NA;
+  constexpr int W3_TN = 32 * NG, W3_TC = 32 * NA;
   constexpr int W3_GRB = W3_TN * 4, W3_ARB = W3_TC * 4;                  // row bytes
   constexpr int W3_GSLOTS = W3_TN / 4, W3_ASLOTS = W3_TC / 4;            // 16-byte slots per row
   constexpr int W3_GJ = W3_PX * W3_GSLOTS / W3_NT;                       // DMA rounds
@@ -220,18 +216,16 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
       }                                                                                                   \
   }
 
-  f32x16 acc[GW][9];
+  f32x16 acc[9];
 #pragma unroll
-  for (int b = 0; b < GW; ++b)
+  for (int t = 0; t < 9; ++t)
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[b][t][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
   // transposed-read lane roles: lane 4q+p of a 16-lane group supplies pixel row q; p >> 1 picks the S16 group of the
   // pair, p & 1 the 8-byte half of its 16 plane bytes
   const int l16 = lane & 15, q = l16 >> 2, p = l16 & 3, gi = l31 >> 4;
-  const int sg = 8 * (wg * GW) + 4 * gi + 2 * (p >> 1);         // logical slot of this lane's hi bytes in a G row (block 0 of the wave)
+  const int sg = 8 * wg + 4 * gi + 2 * (p >> 1);                // logical slot of this lane's hi bytes in a G row
   const int sa = 8 * wa + 4 * gi + 2 * (p >> 1);                // ... in an A row
   // G pixel rows of a read are y*32 + x16 + 4j + q: row & 3 == q, one swizzle per lane.  Fragments per lane half h:
   //   G_hi = GH[8h .. 8h+7]                                   A_x1 = (h ? AL : AH)[0-7]      A_x2 = (h ? AH : AL)[8-15]
@@ -240,9 +234,14 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
   // K order is free as long as both operands agree: the hi*hi MFMA takes its A fragment from the halves of the two
   // cross fragments that hold hi, so a tap costs FOUR transposed reads, not six.  The 2^-11 of the cross terms goes on
   // the whole G cross fragments (hi and lo halves alike), once per k-step.
-  uint32_t g_lane_hi[GW], g_lane_x1[GW], g_lane_x2[GW];       // (per block: the swizzle XORs a bit that adding 8 slots carries into)
+  // One-element arrays filled by one-trip loops, here and for ghi / g1 / g2 in the patch loop: what is left of a form with
+  // two gradient blocks per wave.  As plain scalars the same sums compile to other instructions (the slot arithmetic is
+  // reassociated, an address add moves across a scheduling barrier), and the kernels are held to their measured code
+  // (profiles/wgrad_retire_isa.txt).
+  constexpr int NB = 1;
+  uint32_t g_lane_hi[NB], g_lane_x1[NB], g_lane_x2[NB];
 #pragma unroll
-  for (int b = 0; b < GW; ++b) {
+  for (int b = 0; b < NB; ++b) {
     const int sb = sg + 8 * b;
     g_lane_hi[b] = (uint32_t)(((sb + 0) ^ w3_swz<W3_GRB>(q)) * 16 + (p & 1) * 8 + q * W3_GRB + h * (8 * W3_GRB));
     g_lane_x1[b] = (uint32_t)(((sb + (1 - h)) ^ w3_swz<W3_GRB>(q)) * 16 + (p & 1) * 8 + q * W3_GRB);
@@ -269,8 +268,8 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
   // a full LDS round trip, four times per patch).  Waits are counted: LDS reads return in order, so step U needs
   // everything issued up to A(U) and tolerates what was issued after it.  Issue order around a boundary:
   //   ... A(t7) [step t5, before its wait], G(next) [step t5, after it], A(t8) [t6], A(next t0) [t7], A(next t1) [t8] ...
-  u32x2u ar[3][4], graw[GW][2][6];
-  f16x8u gf_hi[GW], gf_x1[GW], gf_x2[GW];
+  u32x2u ar[3][4], graw[2][6];
+  f16x8u gf_hi, gf_x1, gf_x2;
 #define W3_AREAD(Y0, U, S)                                                                                    \
   {                                                                                                           \
     constexpr int y_ = (Y0) + (U) / 18, xh_ = ((U) / 9) & 1, t_ = (U) % 9;                                    \
@@ -289,46 +288,38 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
   {                                                                                                           \
     constexpr int gp_ = (((Y0) + (HH) / 2) * 32 + 16 * ((HH) & 1)) * W3_GRB;                                  \
     static_assert(gp_ + 12 * W3_GRB < 65536, "ds offset");                                                    \
-    _Pragma("unroll") for (int b_ = 0; b_ < GW; ++b_) {                                                       \
-      graw[b_][S][0] = w3_read_tr16<gp_>(ghi[b_]);                                                            \
-      graw[b_][S][1] = w3_read_tr16<gp_ + 4 * W3_GRB>(ghi[b_]);                                               \
-      graw[b_][S][2] = w3_read_tr16<gp_>(g1[b_]);                                                             \
-      graw[b_][S][3] = w3_read_tr16<gp_ + 4 * W3_GRB>(g1[b_]);                                                \
-      graw[b_][S][4] = w3_read_tr16<gp_ + 8 * W3_GRB>(g2[b_]);                                                \
-      graw[b_][S][5] = w3_read_tr16<gp_ + 12 * W3_GRB>(g2[b_]);                                               \
-    }                                                                                                         \
+    graw[S][0] = w3_read_tr16<gp_>(ghi[0]);                                                                   \
+    graw[S][1] = w3_read_tr16<gp_ + 4 * W3_GRB>(ghi[0]);                                                      \
+    graw[S][2] = w3_read_tr16<gp_>(g1[0]);                                                                    \
+    graw[S][3] = w3_read_tr16<gp_ + 4 * W3_GRB>(g1[0]);                                                       \
+    graw[S][4] = w3_read_tr16<gp_ + 8 * W3_GRB>(g2[0]);                                                       \
+    graw[S][5] = w3_read_tr16<gp_ + 12 * W3_GRB>(g2[0]);                                                      \
   }
 #define W3_STEP(Y0, U)                                                                                        \
   {                                                                                                           \
     constexpr int t_ = (U) % 9, hh_ = (U) / 9;                                                                \
     constexpr bool nxt_ = hh_ + 1 < NH;                                                                       \
     if ((U) + 2 < NU) W3_AREAD(Y0, ((U) + 2 < NU ? (U) + 2 : 0), (((U) + 2) % 3))                             \
-    constexpr int cnt_ = ((U) + 1 < NU ? 4 : 0) + ((U) + 2 < NU ? 4 : 0) + (((t_ == 6 || t_ == 7) && nxt_) ? 6 * GW : 0); \
+    constexpr int cnt_ = ((U) + 1 < NU ? 4 : 0) + ((U) + 2 < NU ? 4 : 0) + (((t_ == 6 || t_ == 7) && nxt_) ? 6 : 0); \
     __builtin_amdgcn_s_waitcnt(0xC07F | ((cnt_ < 15 ? cnt_ : 15) << 8));    /* (lgkmcnt is a 4-bit field: 15 = the most it can tolerate) */ \
     __builtin_amdgcn_sched_barrier(0);                                                                        \
     if (t_ == 0) {                                                                                            \
-      _Pragma("unroll") for (int b_ = 0; b_ < GW; ++b_) {                                                     \
-        gf_hi[b_] = w3_frag(graw[b_][hh_ & 1][0], graw[b_][hh_ & 1][1]);                                      \
-        gf_x1[b_] = w3_frag(graw[b_][hh_ & 1][2], graw[b_][hh_ & 1][3]) * cg;                                 \
-        gf_x2[b_] = w3_frag(graw[b_][hh_ & 1][4], graw[b_][hh_ & 1][5]) * cg;                                 \
-        /* G11: the hi halves of the two cross fragments, GH'[8-15] on the lower lanes and GH'[0-7] on the upper ones */ \
-        if (G11) gf_x1[b_] = upper ? gf_x1[b_] : gf_x2[b_];                                                   \
-      }                                                                                                       \
+      gf_hi = w3_frag(graw[hh_ & 1][0], graw[hh_ & 1][1]);                                                    \
+      gf_x1 = w3_frag(graw[hh_ & 1][2], graw[hh_ & 1][3]) * cg;                                               \
+      gf_x2 = w3_frag(graw[hh_ & 1][4], graw[hh_ & 1][5]) * cg;                                               \
+      /* G11: the hi halves of the two cross fragments, GH'[8-15] on the lower lanes and GH'[0-7] on the upper ones */ \
+      if (G11) gf_x1 = upper ? gf_x1 : gf_x2;                                                                 \
     }                                                                                                         \
     if (t_ == 5 && nxt_) W3_GREAD(Y0, (nxt_ ? hh_ + 1 : 0), ((hh_ + 1) & 1))                                  \
     const f16x8u ax1_ = w3_frag(ar[(U) % 3][0], ar[(U) % 3][1]), ax2_ = w3_frag(ar[(U) % 3][2], ar[(U) % 3][3]); \
     const f16x8u ahi_ = upper ? ax2_ : ax1_;                                                                  \
-    _Pragma("unroll") for (int b_ = 0; b_ < GW; ++b_)                                                         \
-      acc[b_][t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_hi[b_], ahi_, acc[b_][t_], 0, 0, 0);            \
+    acc[t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_hi, ahi_, acc[t_], 0, 0, 0);                          \
     if (G11) {            /* ONE cross MFMA: GH' x AL over the 16 pixels (AL[8-15] on the lower lanes, AL[0-7] on the upper) */ \
       const f16x8u alo_ = upper ? ax1_ : ax2_;                                                                \
-      _Pragma("unroll") for (int b_ = 0; b_ < GW; ++b_)                                                       \
-        acc[b_][t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_x1[b_], alo_, acc[b_][t_], 0, 0, 0);          \
+      acc[t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_x1, alo_, acc[t_], 0, 0, 0);                        \
     } else {                                                                                                  \
-      _Pragma("unroll") for (int b_ = 0; b_ < GW; ++b_)                                                       \
-        acc[b_][t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_x1[b_], ax1_, acc[b_][t_], 0, 0, 0);          \
-      _Pragma("unroll") for (int b_ = 0; b_ < GW; ++b_)                                                       \
-        acc[b_][t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_x2[b_], ax2_, acc[b_][t_], 0, 0, 0);          \
+      acc[t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_x1, ax1_, acc[t_], 0, 0, 0);                        \
+      acc[t_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf_x2, ax2_, acc[t_], 0, 0, 0);                        \
     }                                                                                                         \
     __builtin_amdgcn_sched_barrier(0);                                                                        \
   }
@@ -378,9 +369,9 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
     const uint32_t gst = g_base + (uint32_t)(stage * W3_GSTAGE * 4);
     const uint32_t abase = a_base + (uint32_t)((ROLL ? ring * W3_AGRP : stage * W3_ASTAGE) * 4) + a_lane;
     const uint32_t abase_hi = a_base + (uint32_t)((((ring + 1) & 3) * W3_AGRP) * 4) + a_lane;
-    uint32_t ghi[GW], g1[GW], g2[GW];
+    uint32_t ghi[NB], g1[NB], g2[NB];
 #pragma unroll
-    for (int b = 0; b < GW; ++b) { ghi[b] = gst + g_lane_hi[b]; g1[b] = gst + g_lane_x1[b]; g2[b] = gst + g_lane_x2[b]; }
+    for (int b = 0; b < NB; ++b) { ghi[b] = gst + g_lane_hi[b]; g1[b] = gst + g_lane_x1[b]; g2[b] = gst + g_lane_x2[b]; }
     if (!(a.dbg & 2)) {
       if (0 == wp) { W3_SEQ(0) }                         // (uniform per wave; the rows are literals in the offsets)
       if (NP >= 2 && 1 == wp) { W3_SEQ((NP >= 2 ? RPW : 0)) }
@@ -408,34 +399,32 @@ __global__ __launch_bounds__(64 * NG * NA * NP, (GW == 2 ? 1 : 2)) void wgrad_ta
   const float inv = a.g_inv_scale ? a.g_inv_scale[0] : 1.f;
   const int c = c0 + 32 * wa + l31;
 #pragma unroll
-  for (int b = 0; b < GW; ++b)
+  for (int t = 0; t < 9; ++t) {
+    const int col = t * d.cin + c;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int col = t * d.cin + c;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = row0 + 32 * (wg * GW + b) + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row < d.n && c < d.cin) {
-          // (waves of different row groups hold parts of the SAME outputs - the atomics used to add them: each group its own slab)
-          if (a.slabs) a.slabs[((int64_t)(ms * NP + wp) * d.n + row) * a.kpad + col] = acc[b][t][r] * inv;
-          else unsafeAtomicAdd(d.dw + (int64_t)row * a.kpad + col, acc[b][t][r] * inv);
-        }
+    for (int r = 0; r < 16; ++r) {
+      const int row = row0 + 32 * wg + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (row < d.n && c < d.cin) {
+        // (waves of different row groups hold parts of the SAME outputs - the atomics used to add them: each group its own slab)
+        if (a.slabs) a.slabs[((int64_t)(ms * NP + wp) * d.n + row) * a.kpad + col] = acc[t][r] * inv;
+        else unsafeAtomicAdd(d.dw + (int64_t)row * a.kpad + col, acc[t][r] * inv);
       }
     }
+  }
 }
 
-template <int NG, int NA, int NP, int PH, int GW = 1, int ROLL = 0, int G11 = 0>
+template <int NG, int NA, int NP, int PH, int ROLL = 0, int G11 = 0>
 static int launch_wgrad_tap3(WgradTap3Args a, hipStream_t stream, char* label, int label_len) {
   constexpr int W3_NT = 64 * NG * NA * NP;
-  constexpr int TN = 32 * NG * GW, TC = 32 * NA;
+  constexpr int TN = 32 * NG, TC = 32 * NA;
   constexpr int AJ = ((PH + 2) * W3_HW * (TC / 4) + W3_NT - 1) / W3_NT;
   constexpr size_t lds = (size_t)(2 * PH * W3_PW * TN + (ROLL ? 4 * 2 * W3_HW * TC : 2 * AJ * W3_NT * 4)) * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  auto kern = wgrad_tap3_s16_kernel<NG, NA, NP, PH, GW, ROLL, G11>;
+  auto kern = wgrad_tap3_s16_kernel<NG, NA, NP, PH, ROLL, G11>;
   if (label) {                       // launch nothing: the instance's name, template arguments as the dispatcher writes them
     int n = snprintf(label, label_len, "wgrad_tap3_s16<%d, %d, %d, %d", NG, NA, NP, PH);
-    if ((GW != 1 || ROLL || G11) && n < label_len) n += snprintf(label + n, label_len - n, ", %d", GW);
-    if ((ROLL || G11) && n < label_len) n += snprintf(label + n, label_len - n, ", %d", ROLL);
+    // (the third optional position held a block count per wave that was always 1: the labels keep it)
+    if ((ROLL || G11) && n < label_len) n += snprintf(label + n, label_len - n, ", 1, %d", ROLL);
     if (G11 && n < label_len) n += snprintf(label + n, label_len - n, ", %d", G11);
     if (n < label_len) snprintf(label + n, label_len - n, ">");
     return AMMC_OK;
@@ -460,7 +449,7 @@ static int launch_wgrad_tap3(WgradTap3Args a, hipStream_t stream, char* label, i
   return ammc_launch_status();
 }
 
-// Called by wgrad_tap_s16_try; -12345 = not this kernel's case.
+// Called by wgrad_s16_dispatch (wgrad_s16.hip) for stride-1 3x3 descriptors; -12345 = not this kernel's case.
 // `slabs` / `query`: see WgradTap3Args (query: the return value is the number of patch splits, or -12345)
 // `label` non-null: nothing is launched, no HIP call is made, the instance's name goes to label (AMMC_OK, or -12345)
 int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpad, hipStream_t stream, float* slabs, int query,
@@ -479,10 +468,6 @@ int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpa
   a.tiles_x = d.width / W3_PW;
   a.tiles_y = a.npatch = 0;                                       // set by the launcher (patch height)
   if (d.cin % 64 == 0) {
-    // AMMC_WGRAD_GW: 2 = the four-wave form with two gradient blocks per wave (A/B; round 4)
-    static const int gw = getenv("AMMC_WGRAD_GW") ? atoi(getenv("AMMC_WGRAD_GW")) : 1;
-    // AMMC_WGRAD_ROLL=0: every patch fetches its own four halo rows (the form before round 5; A/B)
-    static const int roll = getenv("AMMC_WGRAD_ROLL") ? atoi(getenv("AMMC_WGRAD_ROLL")) : 1;
     // AMMC_WGRAD_G11=1 (opt-in, round 5): the GRADIENT operand enters the product with its 11-bit hi half only - two MFMAs
     // per 16 pixels of a channel block (GH x AH + GH' x AL) instead of three: 15-19 % off every layer, 3.7 % off the step
     // (59.4-59.8 -> 57.4 ms).  A weight gradient is a leaf, the 2^-12 relative rounding of g does not propagate, and against
@@ -492,11 +477,11 @@ int wgrad_tap3_s16_try(const AmmcWgradDesc& d, const float* g_inv_scale, int kpa
     // training path (tests/test_gpu_train.py: 1e-4 per tensor) see 2.1e-4 - the arithmetic would no longer be
     // fp32-equivalent, whatever the timed batch can resolve.
     static const int g11 = getenv("AMMC_WGRAD_G11") ? atoi(getenv("AMMC_WGRAD_G11")) : 0;
-    if (g11 && roll && d.n % 128 == 0) return launch_wgrad_tap3<4, 2, 1, 2, 1, 1, 1>(a, stream, label, label_len);
-    if (g11 && roll && d.n % 64 == 0) return launch_wgrad_tap3<2, 2, 2, 2, 1, 1, 1>(a, stream, label, label_len);
-    if (d.n % 128 == 0 && gw == 2) return launch_wgrad_tap3<2, 2, 1, 2, 2>(a, stream, label, label_len);
-    if (d.n % 128 == 0) return roll ? launch_wgrad_tap3<4, 2, 1, 2, 1, 1>(a, stream, label, label_len) : launch_wgrad_tap3<4, 2, 1, 2>(a, stream, label, label_len);
-    if (d.n % 64 == 0) return roll ? launch_wgrad_tap3<2, 2, 2, 2, 1, 1>(a, stream, label, label_len) : launch_wgrad_tap3<2, 2, 2, 2>(a, stream, label, label_len);
+    // <NG, NA, NP, PH, ROLL, G11>; the two-row patches always roll
+    if (g11 && d.n % 128 == 0) return launch_wgrad_tap3<4, 2, 1, 2, 1, 1>(a, stream, label, label_len);
+    if (g11 && d.n % 64 == 0) return launch_wgrad_tap3<2, 2, 2, 2, 1, 1>(a, stream, label, label_len);
+    if (d.n % 128 == 0) return launch_wgrad_tap3<4, 2, 1, 2, 1>(a, stream, label, label_len);
+    if (d.n % 64 == 0) return launch_wgrad_tap3<2, 2, 2, 2, 1>(a, stream, label, label_len);
     if (d.n == 32 && d.height % 4 == 0) return launch_wgrad_tap3<1, 2, 4, 4>(a, stream, label, label_len);    // the output layer
     return -12345;
   }

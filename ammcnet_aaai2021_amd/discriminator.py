@@ -115,7 +115,6 @@ class DiscEngine:
         self._scratch: Optional[torch.Tensor] = None
         self._zeros: Optional[torch.Tensor] = None
         self._det_slabs: Dict[int, torch.Tensor] = {}     # `deterministic`: slab workspace of the weight gradients, per HIP stream
-        deterministic_of(module)                           # (refuses AMMC_WGRAD_TAP=2 with the switch on)
         self.slots_created = 0
 
     # ---- plumbing --------------------------------------------------------------------------------------------

@@ -45,14 +45,10 @@ DETERMINISTIC = os.environ.get("AMMC_DETERMINISTIC", "0") != "0"
 
 
 def deterministic_of(module) -> bool:
-    """the switch of `module` (`module.deterministic`; modules without the attribute follow AMMC_DETERMINISTIC), checked
-    against what the mode cannot keep: AMMC_WGRAD_TAP=2 selects a weight-gradient kernel that has only an atomics form"""
+    """the switch of `module`: `module.deterministic`; modules without the attribute follow AMMC_DETERMINISTIC.  Every
+    weight-gradient kernel a process can reach has a deterministic form, so there is nothing to check it against."""
     det = getattr(module, "deterministic", None)
-    det = DETERMINISTIC if det is None else bool(det)
-    if det and os.environ.get("AMMC_WGRAD_TAP", "") == "2":
-        raise RuntimeError("deterministic training: AMMC_WGRAD_TAP=2 selects wgrad_tap_s16, whose weight gradients end in "
-                           "fp32 atomics and have no deterministic form - unset AMMC_WGRAD_TAP or turn `deterministic` off")
-    return det
+    return DETERMINISTIC if det is None else bool(det)
 
 
 class _WS:
@@ -212,7 +208,7 @@ class _Ops:
         d.n, d.cin, d.ntaps, d.a_step = n, cin, ntaps, a_step
         d.g_bs, d.g_rs, d.g_ps = g16.strides
         d.a_bs, d.a_rs, d.a_ps = a16.strides
-        label = ("conv_wgrad_s16 (3x3 weight gradients: wgrad_tap3_s16 / wgrad_tap_s16 instances)" if ntaps == 9 else
+        label = ("conv_wgrad_s16 (3x3 weight gradients: wgrad_tap3_s16 instances)" if ntaps == 9 else
                  "conv_wgrad_s16 (ConvTranspose weight gradients: wgrad_s16)")
         flops = 2.0 * g16.B * g16.H * g16.W * ntaps * (true_nc if true_nc is not None else n * cin)      # unpadded channels
         if out_oihw is not None and ntaps == 9 and a_step == 1:
@@ -1031,7 +1027,6 @@ class TrainEngine:
         if precision not in ("fp32", "s16"):
             raise ValueError("train precision must be 'fp32' (exact fp32 MFMA) or 's16' (split-fp16 MFMA 3x3 layers)")
         self.module, self.kind, self.precision = module, kind, precision
-        deterministic_of(module)            # (refuses AMMC_WGRAD_TAP=2 with the switch on, before anything is allocated)
         self._ws: Dict = {}
         self.generation = 0
 
@@ -1201,7 +1196,6 @@ class BlockEngine:
             raise ValueError(kind)
         self.module, self.kind, self.precision = module, kind, precision
         self.owner = owner if owner is not None else module
-        deterministic_of(self.owner)
         self._ws: Dict = {}
         self.generation = 0
 
@@ -1362,7 +1356,6 @@ class MemoryBlockEngine:
             raise ValueError(kind)
         self.module, self.kind = module, kind
         self.owner = owner if owner is not None else module
-        deterministic_of(self.owner)
         self.precision = "fp32"                     # 1x1 convolutions and the lookups run on the exact-fp32 kernels
         self._ws: Dict = {}
         self.generation = 0

@@ -365,9 +365,9 @@ int64_t ammc_conv_wgrad_s16_slab_floats(const AmmcWgradDesc* desc);
 int ammc_conv_wgrad_s16_slabs(const AmmcWgradDesc* desc, const float* g_inv_scale, float* slabs, int64_t slab_floats,
                               float* dw_oihw, int32_t cout, int32_t cin, void* stream);
 /* Which kernel ammc_conv_wgrad_s16 launches for this descriptor, as the NUL-terminated name of the instance
- * ("wgrad_tap3_s16<2, 2, 2, 2, 1, 1>", "wgrad_tap_s16<8, 1>", "wgrad_s16": template arguments as the dispatcher writes
- * them, trailing defaults left out), without launching anything and without a HIP call: the same argument checks (all
- * four pointers of the descriptor included) and the same dispatch code, environment switches included, with the launch
+ * ("wgrad_tap3_s16<2, 2, 2, 2, 1, 1>", "wgrad_tap3_s16<1, 2, 4, 4>", "wgrad_s16": the instance's parameters <NG, NA, NP,
+ * PH, 1, ROLL, G11>, trailing zeros and the 1 in front of them left out), without launching anything and without a HIP call: the same argument checks (all
+ * four pointers of the descriptor included) and the same dispatch code, its environment switch included, with the launch
  * replaced by the label; the same status codes as ammc_conv_wgrad_s16 for the same descriptor.  out_len >= 48.
  * ammc_conv_wgrad_s16_slabs_variant: the same for ammc_conv_wgrad_s16_slabs (desc->dw is not looked at): the instance's
  * name + "+slabs<k>", k = the slabs the launch writes = ammc_conv_wgrad_s16_slab_floats / (n * kpad); AMMC_EUNSUP where
@@ -385,7 +385,7 @@ int ammc_conv_wgrad_s16_slabs_variant(const AmmcWgradDesc* desc, char* out, int3
  *     alone (shape, n, cin, ntaps; no device query, no environment switch, no launch history).  0 where the descriptor
  *     is refused and where k == 1: the one workgroup per tile then stores straight into dw and `slabs` may be NULL.
  *   ammc_conv_wgrad_s16_det runs wgrad_s16_kernel for EVERY descriptor ammc_conv_wgrad_s16's checks accept - the
- *     halo-patch dispatchers and their switches (AMMC_WGRAD_TAP, ...) are not asked; the stride-1 3x3 layers that have a
+ *     halo-patch dispatcher and its switch (AMMC_WGRAD_G11) are not asked; the stride-1 3x3 layers that have a
  *     slab form are better served by ammc_conv_wgrad_s16_slabs, which is deterministic too.
  *   Status codes: those of the atomics entry for the same descriptor; AMMC_EINVAL when k > 1 and slabs is NULL or
  *     slab_floats is short.

@@ -286,7 +286,7 @@ def test_adam_steps_track_the_oracle():
 
 def test_train_step_at_sizes_the_halo_patch_kernels_take():
     """batch 4 at 128x128: the 128x128 and 64x64 levels go through conv_tap_s16 (fp32 outputs, fp32 residual of the
-    input-gradient convs) and wgrad_tap_s16, which the 64x64 fixtures above are too small to reach; compared with
+    input-gradient convs) and wgrad_tap3_s16, which the 64x64 fixtures above are too small to reach; compared with
     the oracle: outputs and buffers to 1e-4, gradients to the same-branch fp64 truth (tests/truth.py)."""
     sd = S.make_twostream_state()
     net = A.get_twostream((12, 6), (3, 2), 64, 256, 2)

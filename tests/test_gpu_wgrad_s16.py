@@ -17,10 +17,9 @@ DEV = "cuda:0"
 
 
 # W % 32 == 0, H even, cin % 64 == 0 with n % 64 == 0 (or n == 32, H % 4 == 0), and cin <= 32 with n % 64 == 0, H % 4 == 0 go to
-# the three-MFMA halo-patch kernel (csrc/wgrad_tap3_s16.hip), the rest to the im2col one (csrc/wgrad_s16.hip).  NO shape here
-# reaches the four-product kernel (csrc/wgrad_tap_s16.hip): the three-MFMA dispatcher takes everything it would accept, it
-# runs under AMMC_WGRAD_TAP=2 only (=0: im2col for every 3x3).  Both switch forms and the label of every case:
-# tests/test_gpu_wgrad_kernels.py, tests/test_wgrad_cases_host.py
+# the three-MFMA halo-patch kernel (csrc/wgrad_tap3_s16.hip), the rest to the im2col one (csrc/wgrad_s16.hip).  The label of
+# every case, and the im2col kernel on 3x3 shapes the halo-patch one declines: tests/test_gpu_wgrad_kernels.py,
+# tests/test_wgrad_cases_host.py
 @pytest.mark.parametrize("B,H,W,cin,n,gmag", [(2, 32, 32, 64, 128, 1.0), (3, 20, 24, 128, 64, 3e-7), (2, 16, 16, 16, 64, 1e-6),
                                                (1, 9, 7, 32, 32, 1.0), (4, 64, 64, 64, 64, 2e-8), (1, 8, 64, 16, 128, 1e-5),
                                                (2, 16, 32, 128, 64, 1.0), (3, 12, 96, 256, 256, 1e-3),
@@ -73,8 +72,7 @@ def test_wgrad_s16_vs_fp64(B, H, W, cin, n, gmag):
     # hi half, two MFMAs per product block (wgrad_tap3_s16.hip) - a relative 2^-12 rounding of every g, ~1e-4 of max |dw|
     # on these random operands; the default keeps all three products: 3e-6
     import os
-    g11 = (os.environ.get("AMMC_WGRAD_G11", "0") != "0" and os.environ.get("AMMC_WGRAD_ROLL", "1") != "0"
-           and cin % 64 == 0 and n % 64 == 0 and W % 32 == 0 and H % 2 == 0)
+    g11 = os.environ.get("AMMC_WGRAD_G11", "0") != "0" and cin % 64 == 0 and n % 64 == 0 and W % 32 == 0 and H % 2 == 0
     tol = 3e-4 if g11 else 3e-6
     assert err <= tol, (err, tol)
     if g11:
@@ -108,21 +106,9 @@ def test_two_product_form_of_the_gradient_operand():
     import os
     import subprocess
     import sys
-    if "AMMC_WGRAD_G11" in os.environ or "AMMC_WGRAD_ROLL" in os.environ:
+    if "AMMC_WGRAD_G11" in os.environ:
         pytest.skip("already inside a run with a switch set")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k", "test_wgrad_s16_vs_fp64"],
                        env=dict(os.environ, AMMC_WGRAD_G11="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
-
-def test_per_patch_halo_form_still_passes():
-    """`AMMC_WGRAD_ROLL=0` (the A/B switch of the rolling input halo, read once per process): the per-patch halo form of the
-    same kernels against the same fp64 references, in a child process"""
-    import os
-    import subprocess
-    import sys
-    if "AMMC_WGRAD_ROLL" in os.environ or "AMMC_WGRAD_G11" in os.environ:
-        pytest.skip("already inside a run with a switch set")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k", "test_wgrad_s16_vs_fp64"],
-                       env=dict(os.environ, AMMC_WGRAD_ROLL="0"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

@@ -1,7 +1,7 @@
-"""The case table of tests/wgrad_cases.py without a device: every instance the three S16 weight-gradient dispatchers can
+"""The case table of tests/wgrad_cases.py without a device: every instance the S16 weight-gradient dispatch can
 launch has a case, every case reaches the kernel it claims (the library's own dispatch through
-`ammc_conv_wgrad_s16_variant`, which launches nothing and makes no HIP call; the switch forms in a child process with
-the switch set - the dispatchers read them once per process), no default-mode descriptor reaches `wgrad_tap_s16<...>`,
+`ammc_conv_wgrad_s16_variant`, which launches nothing and makes no HIP call; the switch form in a child process with
+the switch set - the dispatcher reads it once per process), every descriptor a halo-patch kernel can take reaches one,
 the fp64 reference agrees with an independent formulation, the truth of every parity case moves by at least ten gates
 when either operand loses its lo half, the placement operands are exact in S16, and both entries refuse what their
 kernels cannot take."""
@@ -23,23 +23,24 @@ CSRC = os.path.join(ROOT, "ammcnet_aaai2021_amd", "csrc")
 
 
 def dispatcher_instances():
-    """the instances the dispatchers can launch, parsed from their `launch_wgrad_tap3<...>` / `launch_wgrad_tap<...>` calls,
-    as the labels the launchers print for them"""
-    def body(name):
-        """the text of <name>.hip from the definition of <name>_try on"""
-        text = open(os.path.join(CSRC, name + ".hip")).read()
-        m = re.search(r"\bint " + name + r"_try\([^;{]*\)\s*\{", text)
-        assert m, f"{name}.hip: the definition of {name}_try was not found"
-        return text[m.start():]
-    t3, t = body("wgrad_tap3_s16"), body("wgrad_tap_s16")
-    norm = lambda m: ", ".join(a.strip() for a in m.group(1).split(","))
-    return ({"wgrad_tap3_s16<%s>" % norm(m) for m in re.finditer(r"launch_wgrad_tap3<([\d, ]+)>\(", t3)} |
-            {"wgrad_tap_s16<%s>" % norm(m) for m in re.finditer(r"launch_wgrad_tap<([\d, ]+)>\(", t)})
+    """the instances the dispatcher can launch, parsed from the `launch_wgrad_tap3<NG, NA, NP, PH[, ROLL[, G11]]>` calls of
+    wgrad_tap3_s16_try, as the labels the launcher prints for them (a literal 1 stands before ROLL)"""
+    text = open(os.path.join(CSRC, "wgrad_tap3_s16.hip")).read()
+    m = re.search(r"\bint wgrad_tap3_s16_try\([^;{]*\)\s*\{", text)
+    assert m, "wgrad_tap3_s16.hip: the definition of wgrad_tap3_s16_try was not found"
+    out = set()
+    for m in re.finditer(r"launch_wgrad_tap3<([\d, ]+)>\(", text[m.start():]):
+        a = [int(v) for v in m.group(1).split(",")]
+        assert 4 <= len(a) <= 6, a
+        roll, g11 = (a + [0, 0])[4:6]
+        shown = a[:4] + ([1, roll] if roll or g11 else []) + ([g11] if g11 else [])
+        out.add("wgrad_tap3_s16<%s>" % ", ".join(str(v) for v in shown))
+    return out
 
 
-def test_the_dispatchers_have_the_eleven_instances_the_table_is_built_for():
-    assert dispatcher_instances() == set(W.TAP3_INSTANCES + W.TAP_INSTANCES)
-    assert len(W.TAP3_INSTANCES + W.TAP_INSTANCES) == 11
+def test_the_dispatcher_has_the_six_instances_the_table_is_built_for():
+    assert dispatcher_instances() == set(W.TAP3_INSTANCES)
+    assert len(W.TAP3_INSTANCES) == 6
 
 
 def test_the_table_covers_every_instance_the_im2col_windows_and_the_slab_form():
@@ -53,14 +54,13 @@ def test_the_table_covers_every_instance_the_im2col_windows_and_the_slab_form():
         assert any(c.inv_null for c in mine), inst                                  # g_inv_scale = NULL, unscaled operands
         if inst != W.IM2COL:
             assert any(c.slab for c in mine), inst
-    for inst in (W.R64, W.R128, W.O32, W.F32C, W.IM2COL, W.TAP8, W.TAP4):           # operand geometry on every default / A/B kernel
+    for inst in (W.R64, W.R128, W.O32, W.F32C, W.IM2COL):                           # operand geometry on every default kernel
         assert {c.geom for c in par if c.label == inst and c.kind == "conv3"} >= {"dense", "slice", "crop"}, inst
     assert any(c.geom == "oddcrop" and c.scaled == "a" for c in par if c.kind == "convt")
     mags = [c.gmag for c in par]
     assert min(mags) == 2e-8 and max(mags) == 1.0
     assert any(c.slab and c.cout and c.cout < c.n for c in par) and any(c.slab and c.cin_true and c.cin_true < c.cin for c in par)
-    assert {c.switch for c in W.CASES} == {"", "AMMC_WGRAD_TAP=2", "AMMC_WGRAD_TAP=0", "AMMC_WGRAD_GW=2", "AMMC_WGRAD_ROLL=0",
-                                           "AMMC_WGRAD_G11=1"}
+    assert {c.switch for c in W.CASES} == {"", "AMMC_WGRAD_G11=1"}
     # the 4x4 window: both strides, an odd input, the first layer's and the head's channel counts
     c4 = [c for c in par if c.kind == "conv4"]
     assert {c.a_step for c in c4} == {1, 2} and any(c.a_odd for c in c4)
@@ -73,11 +73,9 @@ def _check_labels(case, got, slab_got, slab_count):
     src, slab_label = slab_got
     assert (src == 0) == case.slab, (case.name, src, slab_label)
     if case.slab:
-        # the slab entry has its own dispatch (wgrad_tap3_s16_try): the instance is the case's unless the case's switch
-        # bypasses that dispatcher
-        inst = case.label if case.label in W.TAP3_INSTANCES else None
+        # both entries go through wgrad_tap3_s16_try: the instance is the case's
         m = re.fullmatch(r"(wgrad_tap3_s16<[\d, ]+>)\+slabs(\d+)", slab_label)
-        assert m and (inst is None or m.group(1) == inst) and int(m.group(2)) == slab_count >= 1, (case.name, slab_label, slab_count)
+        assert m and m.group(1) == case.label and int(m.group(2)) == slab_count >= 1, (case.name, slab_label, slab_count)
     else:
         assert src == -2 and slab_count == 0
 
@@ -123,10 +121,10 @@ def test_every_switch_case_reaches_the_kernel_it_claims(switch):
         _check_labels(c, tuple(g), tuple(s), n)
 
 
-def test_no_default_mode_descriptor_reaches_the_four_product_halo_patch_kernels():
-    """the routing finding: `wgrad_tap3_s16_try` accepts every descriptor `wgrad_tap_s16_try` would, so `wgrad_tap_s16<8, 1>`
-    and `<4, 2>` run under AMMC_WGRAD_TAP=2 only.  Through the library's own dispatch, over cin 8 .. 512, n 32 .. 512 in steps
-    of 32, H 1 .. 12, W in {7, 32, 64}."""
+def test_every_descriptor_a_halo_patch_kernel_can_take_reaches_one():
+    """the routing over a grid of descriptors: the default labels are the four halo-patch instances and the im2col form and
+    nothing else, and what the retired four-product dispatcher accepted lands on a three-MFMA instance.  Through the
+    library's own dispatch, over cin 8 .. 512, n 32 .. 512 in steps of 32, H 1 .. 12, W in {7, 32, 64}."""
     if any(k in os.environ for k in W.SWITCHES):
         pytest.skip("a dispatch switch is set in this process")
     lib = _lib.load()
@@ -140,8 +138,7 @@ def test_no_default_mode_descriptor_reaches_the_four_product_halo_patch_kernels(
                     assert lib.ammc_conv_wgrad_s16_variant(C.byref(d), buf, 96) == 0
                     lab = buf.value.decode()
                     seen[lab] = seen.get(lab, 0) + 1
-                    assert not lab.startswith("wgrad_tap_s16<"), (cin, n, H, Wd, lab)
-                    # what the four-product dispatcher would accept is taken by the three-MFMA one
+                    # what the four-product dispatcher accepted is taken by the three-MFMA one
                     if H % 4 == 0 and Wd % 32 == 0 and ((n % 128 == 0 and cin % 16 == 0) or (n % 64 == 0 and cin % 32 == 0)):
                         assert lab.startswith("wgrad_tap3_s16<"), (cin, n, H, Wd, lab)
     assert set(seen) == {W.R64, W.R128, W.O32, W.F32C, W.IM2COL}, seen

@@ -1,13 +1,12 @@
-"""Cases of the S16 weight-gradient kernels - csrc/wgrad_tap3_s16.hip (nine instances + the slab reduce),
-wgrad_tap_s16.hip (two instances), wgrad_s16.hip (the im2col form: 3x3, 4x4 stride 1 | 2, the 2x2 stride-2 window of a
-ConvTranspose) - behind `ammc_conv_wgrad_s16` / `ammc_conv_wgrad_s16_slabs`, shared by tests/test_wgrad_cases_host.py
+"""Cases of the S16 weight-gradient kernels - csrc/wgrad_tap3_s16.hip (six instances + the slab reduce),
+wgrad_s16.hip (the im2col form: 3x3, 4x4 stride 1 | 2, the 2x2 stride-2 window of a ConvTranspose) - behind `ammc_conv_wgrad_s16` / `ammc_conv_wgrad_s16_slabs`, shared by tests/test_wgrad_cases_host.py
 (labels, routing, references, sensitivity, refusals: no device) and tests/test_gpu_wgrad_kernels.py (the kernels against
 fp64).  A helper module like tests/patch_cases.py, not a test.
 
 A case is one launch as the training engine builds it: the shape, the padded and the true channel counts, where the
 operands live (dense, the upper half of a buffer twice as wide, a window of a larger buffer, the ConvTranspose's odd
 crop), which operand carries the power-of-two scale, the label `ammc_conv_wgrad_s16_variant` must answer, whether the slab
-entry takes it, and the environment switch (read once per process by the dispatchers) under which it runs.
+entry takes it, and the environment switch (read once per process by the dispatcher) under which it runs.
 
 Kinds (H, W: the pixel space of g)
   conv3  dW[o][c][r][s] = sum G[b][y][x][o] A[b][y + r - 1][x + s - 1][c]         Conv2d(k 3, padding 1)
@@ -38,19 +37,15 @@ SENS_MIN = 10              # an operand reduced to its hi half must move the fp6
 DEV = "cuda:0"
 SENT = 0x7FC07FC0
 PAD = 1024                 # floats (4 KB) of sentinel before and behind every guarded buffer
-SWITCHES = ("AMMC_WGRAD_TAP", "AMMC_WGRAD_GW", "AMMC_WGRAD_ROLL", "AMMC_WGRAD_G11")
+SWITCHES = ("AMMC_WGRAD_G11",)
 
 _T3 = "wgrad_tap3_s16<%s>"
 R64, R128 = _T3 % "2, 2, 2, 2, 1, 1", _T3 % "4, 2, 1, 2, 1, 1"          # the rolling-halo instances (default)
 O32, F32C = _T3 % "1, 2, 4, 4", _T3 % "2, 1, 4, 4"                      # output layer; first layers (cin <= 32)
-P64, P128 = _T3 % "2, 2, 2, 2", _T3 % "4, 2, 1, 2"                      # AMMC_WGRAD_ROLL=0
-GW2 = _T3 % "2, 2, 1, 2, 2"                                             # AMMC_WGRAD_GW=2
 G64, G128 = _T3 % "2, 2, 2, 2, 1, 1, 1", _T3 % "4, 2, 1, 2, 1, 1, 1"    # AMMC_WGRAD_G11=1
-TAP8, TAP4 = "wgrad_tap_s16<8, 1>", "wgrad_tap_s16<4, 2>"               # AMMC_WGRAD_TAP=2
 IM2COL = "wgrad_s16"
-TAP3_INSTANCES = [R64, R128, O32, F32C, P64, P128, GW2, G64, G128]
-TAP_INSTANCES = [TAP8, TAP4]
-INSTANCES = TAP3_INSTANCES + TAP_INSTANCES + [IM2COL]
+TAP3_INSTANCES = [R64, R128, O32, F32C, G64, G128]
+INSTANCES = TAP3_INSTANCES + [IM2COL]
 
 
 @dataclass(frozen=True)
@@ -71,7 +66,7 @@ class Case:
     geom: str = "dense"      # dense | slice (upper half of a 2x-wide buffer) | crop (window of a larger buffer) | oddcrop (convt)
     scaled: str = "g"        # which operand went through ammc_split_rows_scaled_f32: g | a | "" (g_inv_scale = NULL)
     slab: bool = False       # the slab entry takes it
-    switch: str = ""         # "" or "AMMC_WGRAD_TAP=2", ...: the process environment it runs under
+    switch: str = ""         # "" or "AMMC_WGRAD_G11=1": the process environment it runs under
     hot: tuple = ()          # placement case: ((b, y, x), ...) - g is `gmag` at spot j in channel j and zero elsewhere
 
     @property
@@ -130,7 +125,7 @@ def _default_cases():
         c3("first-cin16of12-n128-b3", 3, 12, 32, 128, 16, F32C, cin_true=12, scaled="", geom="slice", **sl),
         c3("first-cin32-n64-b3", 3, 12, 32, 64, 32, F32C, gmag=3e-4, geom="crop", **sl),
         c3("first-cin8of3-n128-b3", 3, 12, 32, 128, 8, F32C, cin_true=3, gmag=1e-1, **sl),
-        # ---- the im2col form, 3x3: what both halo-patch dispatchers decline ---------------------------------------------------------
+        # ---- the im2col form, 3x3: what the halo-patch dispatcher declines ----------------------------------------------------------
         c3("im2col-m63", 1, 9, 7, 32, 32, IM2COL),                                                            # one short chunk
         c3("im2col-n96", 1, 4, 32, 96, 64, IM2COL, gmag=1e-5, geom="slice"),                                  # n % 64
         c3("im2col-n32-h6", 1, 6, 32, 32, 64, IM2COL, cout=3, scaled="", geom="crop"),                        # H % 4
@@ -161,33 +156,6 @@ def _switch_cases(default):
 
     def add(switch, tag, base, label, **kw):
         out.append(replace(by[base], name=f"{tag}-{base}", switch=switch, label=label, **kw))
-    # AMMC_WGRAD_TAP=2: the four-product halo-patch kernels only (no slab form: the three-MFMA kernel's)
-    c3 = lambda name, B, H, W, n, cin, label, **kw: _c(name, "conv3", B, H, W, n, cin, label, switch="AMMC_WGRAD_TAP=2", **kw)
-    out += [
-        c3("tap8-n128-cin16", 1, 4, 32, 128, 16, TAP8, cin_true=12, gmag=1e-4, slab=True),
-        c3("tap8-n128-cin16-b2", 2, 8, 64, 128, 16, TAP8, scaled="", geom="slice", slab=True),
-        c3("tap8-n128-cin64", 1, 4, 32, 128, 64, TAP8, gmag=2e-8, geom="crop", slab=True),
-        c3("tap8-n128-cin64-b2", 2, 8, 64, 128, 64, TAP8, gmag=1e-2, slab=True),
-        c3("tap4-n64-cin32", 1, 4, 32, 64, 32, TAP4, scaled="", slab=True),
-        c3("tap4-n64-cin32-b2", 2, 8, 64, 64, 32, TAP4, gmag=1e-6, geom="crop", slab=True),
-        c3("tap4-n64-cin128", 1, 4, 32, 64, 128, TAP4, gmag=1e-3, geom="slice", slab=True),
-        c3("tap4-n64-cin128-b2", 2, 8, 64, 64, 128, TAP4, gmag=3e-7, slab=True),
-        c3("place-tap8-one", 2, 8, 64, 128, 16, TAP8, hot=HOT, slab=True),
-        c3("place-tap8-tiny", 2, 8, 64, 128, 16, TAP8, hot=HOT, gmag=TINY, slab=True),
-        c3("place-tap4-one", 2, 8, 64, 64, 32, TAP4, hot=HOT, slab=True),
-        c3("place-tap4-tiny", 2, 8, 64, 64, 32, TAP4, hot=HOT, gmag=TINY, slab=True),
-    ]
-    # AMMC_WGRAD_TAP=0: the im2col form for every 3x3 (the slab entry has its own dispatch and still takes the descriptor)
-    for c in default:                   # every case of the four halo-patch kernels, parity and placement
-        if c.kind == "conv3" and c.label != IM2COL:
-            add("AMMC_WGRAD_TAP=0", "tap0", c.name, IM2COL)
-    for base in ("r128-one-patch", "r128-n256-cin128", "r128-crop", "place-r128-one", "place-r128-tiny"):
-        add("AMMC_WGRAD_GW=2", "gw2", base, GW2)
-    for base, lab in (("r64-one-patch", P64), ("r64-run-crosses-columns-and-images", P64), ("r64-split-starts-mid-column", P64),
-                      ("r64-one-patch-columns", P64), ("r64-n192", P64), ("place-r64-one", P64), ("place-r64-tiny", P64),
-                      ("r128-one-patch", P128), ("r128-n256-cin128", P128), ("r128-crop", P128), ("place-r128-one", P128),
-                      ("place-r128-tiny", P128)):
-        add("AMMC_WGRAD_ROLL=0", "roll0", base, lab)
     for base, lab in (("r64-one-patch", G64), ("r64-run-crosses-columns-and-images", G64), ("r64-split-starts-mid-column", G64),
                       ("r64-one-patch-columns", G64), ("r64-n192", G64), ("place-r64-one", G64), ("place-r64-tiny", G64),
                       ("r128-one-patch", G128), ("r128-n256-cin128", G128), ("r128-crop", G128), ("place-r128-one", G128),

@@ -1,5 +1,5 @@
 """time one 3x3 S16 weight-gradient layer:  python tools/wgrad_bench.py B H W cin n [reps]
-env: AMMC_WGRAD_TAP=2 (four-product halo-patch kernels), =0 (im2col kernel)"""
+env: WGRAD_SLABS=0 (the atomics entry instead of the training path's slab form), AMMC_WGRAD_G11=1 (two-product form)"""
 import ctypes as C
 import os
 import sys
