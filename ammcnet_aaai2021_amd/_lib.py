@@ -186,6 +186,10 @@ SIGNATURES = {
     "ammc_curve_sweep_max_class": (C.c_int, []),
     "ammc_curve_sweep_workspace_bytes": (C.c_int64, [_i32, _i32, _i32]),
     "ammc_curve_sweep_f32": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    "ammc_video_pairs_max_segment": (C.c_int, []),
+    "ammc_video_pairs_max_videos": (C.c_int, []),
+    "ammc_video_pairs_f32": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _i32, _i32, _p, _p]),
+    "ammc_bootstrap_pairs_i64": (C.c_int, [_p, _i32, _i32, _p, _i32, _p, _p]),
     "ammc_pixel_scores_f32": (C.c_int, [_p, _i64, _p, _i64] + [_i32] * 5 + [_p, _p, _p, _p, _p]),
     "ammc_render_stats_f32": (C.c_int, [_p, _i64] * 4 + [_i32] * 3 + [_f32, _f32, _p, _p]),
     "ammc_render_panels_u8": (C.c_int, [_p, _i64] * 4 + [_i32] * 3 + [_f32, _f32, _p, _i32, _i32, _p, _i32, _p, _p, _p, _f32,

@@ -1353,6 +1353,204 @@ def sweep_curves(records: dict, gt: Sequence[np.ndarray], channels: Sequence[str
     return out
 
 
+# ---- macro AUC and video-bootstrap confidence intervals from per-video pair counts ----
+# Frames of one video are correlated, so the sampling unit of an error bar is the video.  `ops.video_pairs` splits the
+# sweep's count by the video of either frame (a V x V integer block per grid point); its diagonal gives the per-video and
+# the macro AUC, and `ops.bootstrap_pairs` - a bilinear form in the replica's multiplicities - the AUC of every bootstrap
+# replica without resampling a frame.  Passes of their own: `sweep_fusion` and `sweep_curves` above are untouched.
+
+def video_offsets(gt: Sequence[np.ndarray], labels_positive: int = 0) -> dict:
+    """Where each video's frames stand in the class index lists of a sweep: `n_pos`, `n_neg` (int64 [V], the video's
+    scored frames of either class) and `pos_off`, `neg_off` (int64 [V + 1], their running sums from 0).  `gt[v]`: the
+    per-frame labels of video v; a frame is positive iff its label equals `labels_positive` (0: the normal class).  The
+    first DECIDABLE_IDX frames of each video are not scored, as `sweep_fusion` drops them: a shorter video has none."""
+    n_pos = np.array([int((np.asarray(g)[DECIDABLE_IDX:] == labels_positive).sum()) for g in gt], dtype=np.int64)
+    n_neg = np.array([int((np.asarray(g)[DECIDABLE_IDX:] != labels_positive).sum()) for g in gt], dtype=np.int64)
+    return {"n_pos": n_pos, "n_neg": n_neg, "pos_off": np.concatenate([[0], np.cumsum(n_pos)]).astype(np.int64),
+            "neg_off": np.concatenate([[0], np.cumsum(n_neg)]).astype(np.int64)}
+
+
+def bootstrap_multiplicities(V: int, replicas: int, seed: int) -> np.ndarray:
+    """int32 [replicas, V]: how often each of V videos is drawn in each replica of a bootstrap of V draws with
+    replacement - one multinomial row per replica from PCG64(seed): the same seed gives the same table"""
+    if V < 1 or replicas < 1:
+        raise ValueError(f"bootstrap_multiplicities: V >= 1 and replicas >= 1, got {V} and {replicas}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return rng.multinomial(V, np.full(V, 1 / V), size=replicas).astype(np.int32)
+
+
+def _interval(x: np.ndarray, level: float) -> np.ndarray:
+    """percentiles (1 - level) / 2 and (1 + level) / 2 over axis 0, numpy's default linear rule, float64 -> [..., 2]"""
+    q = np.percentile(np.asarray(x, dtype=np.float64), [50.0 * (1.0 - level), 50.0 * (1.0 + level)], axis=0)
+    return np.moveaxis(q, 0, -1)
+
+
+def replica_statistics(two_u_r, diag, mult, n_pos, n_neg, level: float = 0.95, grid_points: Optional[int] = None,
+                       best: Optional[int] = None) -> dict:
+    """What a video bootstrap says about M points, on the host in float64 - a pure function of its arguments:
+    `two_u_r` int64 [B, M] (`ops.bootstrap_pairs`' table), `diag` int64 [M, V] (the diagonals of the pair blocks), `mult`
+    [B, V], `n_pos` / `n_neg` [V] (P_a, Q_a).  Replica r has P_r = sum m[a] P_a, Q_r = sum m[b] Q_b, the AUC
+    two_u_r / (2 P_r Q_r) and the macro AUC sum m[a] auc_a / sum m[a] over the scored videos (both classes present).  A
+    replica with P_r = 0, Q_r = 0 or no scored video has neither: it is dropped from every statistic and counted; more
+    than half of them dropped is a ValueError.  Returns `usable` (bool [B]), `replicas_dropped`, `per_video_auc` [M, V]
+    (NaN where a class is missing), `macro_auc` [M], `auc_r` and `macro_auc_r` [usable, M], `auc_ci` and `macro_auc_ci`
+    [M, 2] (`level`), and - with `best`, an index below `grid_points` (default M) - `best_share`: the share of usable
+    replicas whose own first argmax over the first `grid_points` points is `best`."""
+    two_u_r, diag = np.asarray(two_u_r, dtype=np.int64), np.asarray(diag, dtype=np.int64)
+    mult, n_pos, n_neg = np.asarray(mult, dtype=np.int64), np.asarray(n_pos, dtype=np.int64), np.asarray(n_neg, dtype=np.int64)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"replica_statistics: 0 < level < 1, got {level}")
+    scored = (n_pos > 0) & (n_neg > 0)
+    p_r, q_r, s_r = mult @ n_pos, mult @ n_neg, mult[:, scored].sum(1)
+    usable = (p_r > 0) & (q_r > 0) & (s_r > 0)
+    dropped = int((~usable).sum())
+    if 2 * dropped > mult.shape[0]:
+        raise ValueError(f"replica_statistics: {dropped} of {mult.shape[0]} replicas have no AUC (a class or every scored "
+                         f"video missing): too few videos hold both classes for a bootstrap over videos")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_video = np.where(scored, diag / (2.0 * n_pos * n_neg), np.nan)
+    auc_r = two_u_r[usable] / (2.0 * p_r[usable] * q_r[usable])[:, None]
+    m_s = mult[usable][:, scored].astype(np.float64)
+    macro_r = (m_s @ per_video[:, scored].T) / m_s.sum(1)[:, None]
+    out = {"usable": usable, "replicas_dropped": dropped, "per_video_auc": per_video,
+           "macro_auc": per_video[:, scored].mean(1) if scored.any() else np.full(diag.shape[0], np.nan),
+           "auc_r": auc_r, "macro_auc_r": macro_r, "auc_ci": _interval(auc_r, level), "macro_auc_ci": _interval(macro_r, level)}
+    if best is not None:
+        n_grid = auc_r.shape[1] if grid_points is None else grid_points
+        out["best_share"] = float((np.argmax(auc_r[:, :n_grid], axis=1) == best).mean())
+    return out
+
+
+def bootstrap_delta(res: dict, i, j) -> dict:
+    """mean and confidence interval (`res["level"]`) of the paired difference auc_r[i] - auc_r[j] over the usable replicas
+    of a `sweep_videos` result; `i`, `j`: grid indices (g, s), flat indices in grid order, or "lam_map" """
+    S = res["auc"].shape[1]
+
+    def flat(x):
+        if isinstance(x, str):
+            if x != "lam_map" or "at_lam_map" not in res:
+                raise ValueError(f"bootstrap_delta: no point {x!r} in this result")
+            return res["auc"].size
+        return int(x[0]) * S + int(x[1]) if isinstance(x, (tuple, list)) else int(x)
+    d = res["replica_auc"][:, flat(i)] - res["replica_auc"][:, flat(j)]
+    return {"mean": float(d.mean()), "ci": [float(x) for x in _interval(d, res["level"])]}
+
+
+def sweep_videos(records: dict, gt: Sequence[np.ndarray], channels: Sequence[str] = ("rgb_img_pred", "rgb_fea_comm"),
+                 weights=None, smooth: Optional[Sequence[float]] = None, replicas: int = 1000, seed: int = 0, level: float = 0.95,
+                 max_workspace_bytes: int = 256 << 20, device=None) -> dict:
+    """The micro and the macro frame-level AUC of the fused score at every point of a grid, with percentile confidence
+    intervals from a bootstrap over VIDEOS (`ops.video_pairs`, then `ops.bootstrap_pairs`).  Inputs, channel handling and
+    refusals as `sweep_fusion`; for two channels of a dataset in LAM_MAP the published pair is one more point behind the
+    grid, so it sees the same `replicas` multiplicity rows (`bootstrap_multiplicities(V, replicas, seed)`).  The grid runs
+    in chunks of points whose V x V blocks fit `max_workspace_bytes`; the values do not depend on the chunking.  Returns
+    `auc` (float64 [G, S], `sweep_fusion`'s: `two_u`, the block sums, are its integers), `macro_auc` [G, S] (the mean of
+    the per-video AUCs over the videos with both classes), `auc_ci`, `macro_auc_ci` [G, S, 2], `videos`, `videos_scored`,
+    `n_pos`, `n_neg`, `video_n_pos`, `video_n_neg`, `weights`, `lam_smooth`, `best` (first maximum of `auc` in grid order:
+    {weights, lam_smooth, index, auc, macro_auc, auc_ci, macro_auc_ci, per_video_auc [V] - NaN where a class is missing
+    -, pairs [V, V]}), `best_macro` (the same at the first maximum of `macro_auc`, without the block), `best_share` (the
+    share of usable replicas whose own first argmax over the grid is `best`'s index), `replicas`, `replicas_dropped`,
+    `seed`, `level`, `replica_auc` (float64 [usable, G * S (+ 1)]: what `bootstrap_delta` reads), `video_ms` (the
+    launches between device events) and, with a published pair, `at_lam_map` (as `best`, without index) and
+    `delta_best_vs_lam_map` = {mean, ci}.  The HIP passes are the only implementation: a GPU is required."""
+    from . import ops
+    channels = tuple(channels)
+    chan = fusion_channels(records, channels)
+    labels = np.concatenate([np.asarray(g)[DECIDABLE_IDX:] for g in gt])
+    K, N = chan.shape
+    if labels.shape[0] != N:
+        raise ValueError(f"sweep_videos: {labels.shape[0]} labels for {N} scored frames")
+    if not np.isfinite(chan).all():
+        bad = [c for c, row in zip(channels, chan) if not np.isfinite(row).all()]
+        raise ValueError(f"sweep_videos: non-finite normalised scores in {bad} (a constant record, or a NaN / inf in it)")
+    pos, neg = np.flatnonzero(labels == 0), np.flatnonzero(labels != 0)
+    if pos.size == 0 or neg.size == 0:
+        raise ValueError("sweep_videos: the labels hold one class only: the AUC is undefined")
+    if replicas < 1 or not 0.0 < level < 1.0:
+        raise ValueError(f"sweep_videos: replicas >= 1 and 0 < level < 1, got {replicas} and {level}")
+    vo = video_offsets(gt, 0)
+    V = len(gt)
+    if V > ops.VIDEO_PAIRS_MAX_VIDEOS:
+        raise ValueError(f"sweep_videos: {V} videos, ops.video_pairs takes at most {ops.VIDEO_PAIRS_MAX_VIDEOS}")
+    grid = fusion_grid(K)
+    w = grid["weights"] if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1, K))
+    lam_smooth = list(grid["lam_smooth"] if smooth is None else smooth)
+    sm = smoothing_pairs(lam_smooth)
+    G, S = len(w), len(sm)
+    lam = LAM_MAP.get(records.get("dataset")) if K == 2 else None
+    block = V * V * 8
+    fit = max_workspace_bytes // block
+    if fit < 1:
+        raise ValueError(f"sweep_videos: max_workspace_bytes = {max_workspace_bytes} is below one grid point's block of {block} bytes")
+    mult = bootstrap_multiplicities(V, replicas, seed)
+    for m in mult:                                        # the precondition of ammc_bootstrap_pairs_i64, in Python integers
+        if 2 * int(m @ vo["n_pos"]) * int(m @ vo["n_neg"]) >= 1 << 63:
+            raise ValueError("sweep_videos: a replica's 2 P_r Q_r does not fit int64")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(dev)
+    d_chan, d_pos, d_neg = up(chan, torch.float32), up(pos, torch.int32), up(neg, torch.int32)
+    d_poff, d_noff = up(vo["pos_off"], torch.int32), up(vo["neg_off"], torch.int32)
+    d_w, d_sm = up(w, torch.float32), up(sm, torch.float32)
+    d_mult = up(np.concatenate([mult, np.ones((1, V), dtype=np.int32)]), torch.int32)       # last row: the block sum itself
+    chunks = [(g0, min(g0 + fit // S, G), 0, S) for g0 in range(0, G, fit // S)] if fit >= S else \
+        [(g0, g0 + 1, s0, min(s0 + fit, S)) for g0 in range(G) for s0 in range(0, S, fit)]
+    points = G * S + (1 if lam is not None else 0)
+    diag, table = np.empty((points, V), dtype=np.int64), np.empty((replicas + 1, points), dtype=np.int64)
+
+    def launch(dw, dsm):
+        """(diagonals [points, V], replica table [B + 1, points], the blocks on the device, ms) of a sub-grid"""
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        d_c = ops.video_pairs(d_chan, d_pos, d_neg, d_poff, d_noff, dw, dsm)
+        d_t = ops.bootstrap_pairs(d_c.view(-1, V, V), d_mult)
+        t1.record()
+        dg, tb = d_c.view(-1, V, V).diagonal(dim1=1, dim2=2).cpu().numpy(), d_t.cpu().numpy()
+        return dg, tb, d_c, t0.elapsed_time(t1)
+    ms = 0.0
+    with torch.cuda.device(dev):
+        for g0, g1, s0, s1 in chunks:
+            dg, tb, _, t = launch(d_w[g0:g1], d_sm[s0:s1])
+            at = (np.arange(g0, g1)[:, None] * S + np.arange(s0, s1)[None, :]).reshape(-1)
+            diag[at], table[:, at] = dg, tb
+            ms += t
+        two_u = table[replicas, :G * S].reshape(G, S).copy()
+        denom = 2.0 * float(pos.size) * float(neg.size)
+        auc = two_u.astype(np.float64) / denom
+        gi, si = (int(x) for x in np.unravel_index(int(np.argmax(auc)), auc.shape))
+        kept = {"best": launch(d_w[gi:gi + 1], d_sm[si:si + 1])[2].cpu().numpy()[0, 0]}       # the block kept at `best`
+        if lam is not None:
+            w_lam, sm_lam = np.array([[1 - lam[0], lam[0]]], dtype=np.float32), smoothing_pairs([lam[1]])
+            dg, tb, d_c, t = launch(up(w_lam, torch.float32), up(sm_lam, torch.float32))
+            diag[G * S], table[:, G * S], kept["lam_map"] = dg[0], tb[:, 0], d_c.cpu().numpy()[0, 0]
+            ms += t
+    st = replica_statistics(table[:replicas], diag, mult, vo["n_pos"], vo["n_neg"], level, grid_points=G * S, best=gi * S + si)
+
+    def point(at, wv, l2, block=None):
+        out = {"weights": [float(x) for x in wv], "lam_smooth": float(l2), "auc": float(table[replicas, at] / denom),
+               "macro_auc": float(st["macro_auc"][at]), "auc_ci": [float(x) for x in st["auc_ci"][at]],
+               "macro_auc_ci": [float(x) for x in st["macro_auc_ci"][at]], "per_video_auc": st["per_video_auc"][at].copy()}
+        if block is not None:
+            out["pairs"] = block
+        return out
+    macro = st["macro_auc"][:G * S].reshape(G, S)
+    mg, msi = (int(x) for x in np.unravel_index(int(np.argmax(macro)), macro.shape))
+    out = {"two_u": two_u, "auc": auc, "macro_auc": macro, "auc_ci": st["auc_ci"][:G * S].reshape(G, S, 2),
+           "macro_auc_ci": st["macro_auc_ci"][:G * S].reshape(G, S, 2), "videos": V,
+           "videos_scored": int(((vo["n_pos"] > 0) & (vo["n_neg"] > 0)).sum()), "n_pos": int(pos.size), "n_neg": int(neg.size),
+           "video_n_pos": vo["n_pos"], "video_n_neg": vo["n_neg"], "channels": channels, "weights": w, "lam_smooth": lam_smooth,
+           "best": dict(point(gi * S + si, w[gi], lam_smooth[si], kept["best"]), index=(gi, si)),
+           "best_macro": dict(point(mg * S + msi, w[mg], lam_smooth[msi]), index=(mg, msi)),
+           "best_share": st["best_share"], "replicas": int(replicas), "replicas_dropped": st["replicas_dropped"], "seed": int(seed),
+           "level": float(level), "replica_auc": st["auc_r"], "video_ms": float(ms)}
+    if lam is not None:
+        out["at_lam_map"] = point(G * S, w_lam[0], lam[1], kept["lam_map"])
+        out["lam_map"] = tuple(lam)
+        out["delta_best_vs_lam_map"] = bootstrap_delta(out, (gi, si), "lam_map")
+    return out
+
+
 # ---- pixel-level evaluation: mask-aware frame scores from the error maps (DESIGN.md section 5.21) ----
 # A pass of its own behind the evaluation forward and `ops.error_maps` (`ops.pixel_scores`, csrc/pixel_scores.hip): nothing
 # above is touched.  The pixel-level criterion (Mahadevan et al.) at the fraction num / den: a frame with ground-truth

@@ -13,6 +13,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -321,6 +322,8 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, map: bool = False, out: dict 
 
 FUSION_MAX_CHANNELS = 8
 FUSION_MAX_SORTED = 32768    # `ammc_fusion_sweep_max_sorted()`: the smaller class is sorted in one workgroup's LDS
+VIDEO_PAIRS_MAX_SEGMENT = 32768   # `ammc_video_pairs_max_segment()`: one video's frames of the smaller class, sorted in LDS
+VIDEO_PAIRS_MAX_VIDEOS = 1024     # `ammc_video_pairs_max_videos()`: a workgroup keeps one int64 total per video in LDS
 
 
 def _sweep_args(what: str, chan, pos_idx, neg_idx, weights, smooth):
@@ -412,6 +415,103 @@ def curve_sweep(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tensor
             _ptr(res["two_u"].view(-1)[at:]), _ptr(res["pts"].view(-1, 4)[at:]), _ptr(res["thr"].view(-1, 2)[at:]),
             _ptr(res["sums"].view(-1, 2)[at:]), _ptr(ws), ws.numel(), stream), "curve_sweep")
     return res
+
+
+# ---- per-video pair counts and their bootstrap form (csrc/video_pairs.hip) ----------------------
+
+def _video_offsets(what: str, name: str, off, V, count: int, dev):
+    """one offset vector of `video_pairs` -> (V, the vector as given or as a host int64 array, the host array or None).
+    A list or a CPU tensor is checked here; a device tensor only for what needs no read-back."""
+    if isinstance(off, torch.Tensor) and off.is_cuda:
+        if off.dim() != 1 or off.dtype != torch.int32 or off.device != dev or not off.is_contiguous() or off.numel() < 2:
+            raise ValueError(f"{what}: {name} must be a contiguous int32 vector of V + 1 >= 2 entries on {dev}")
+        host = None
+    else:
+        if isinstance(off, torch.Tensor):
+            if off.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{what}: {name} must hold integers, got {off.dtype}")
+            off = off.numpy()
+        host = np.asarray(off)
+        if host.ndim != 1 or host.size < 2 or host.dtype.kind not in "iu":
+            raise ValueError(f"{what}: {name} must be a vector of V + 1 >= 2 integers")
+        host = host.astype(np.int64)
+        if host[0] != 0 or host[-1] != count or (np.diff(host) < 0).any():
+            raise ValueError(f"{what}: {name} must be non-decreasing from 0 to {count}, got {host[0]} .. {host[-1]}")
+    n = (off.numel() if host is None else host.size) - 1
+    if V is not None and n != V:
+        raise ValueError(f"{what}: pos_off and neg_off must both have V + 1 entries, got {V + 1} and {n + 1}")
+    return n, off, host
+
+
+def video_pairs(chan: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tensor, pos_off, neg_off, weights: torch.Tensor,
+                smooth: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """`fusion_sweep`'s count split by the video of either frame (csrc/video_pairs.hip; the definition is in
+    include/ammc_hip.h): int64 [G, S, V, V], entry [a, b] the count over the positive frames of video a and the negative
+    frames of video b.  `chan`, `pos_idx`, `neg_idx`, `weights`, `smooth` as `fusion_sweep` takes them, the index lists in
+    video order.  `pos_off` / `neg_off`: V + 1 offsets into them, non-decreasing from 0 to P (Q) - a list, an array or a
+    CPU tensor (checked here, then uploaded) or an int32 device vector (not checked: that would wait for the device; only
+    when the smaller class exceeds VIDEO_PAIRS_MAX_SEGMENT is the vector read back, for its longest segment).  The block
+    sums are `fusion_sweep`'s integers.  One launch on torch's current stream, every element written once (`out`, when
+    given: contiguous int64 [G, S, V, V], nothing to clear).  V <= VIDEO_PAIRS_MAX_VIDEOS and a video's frames of the
+    smaller class <= VIDEO_PAIRS_MAX_SEGMENT: ValueError beyond."""
+    K, N, P, Q, G, S, rs = _sweep_args("video_pairs", chan, pos_idx, neg_idx, weights, smooth)
+    dev = chan.device
+    V, pos_off, pos_host = _video_offsets("video_pairs", "pos_off", pos_off, None, P, dev)
+    V, neg_off, neg_host = _video_offsets("video_pairs", "neg_off", neg_off, V, Q, dev)
+    if V > VIDEO_PAIRS_MAX_VIDEOS:
+        raise ValueError(f"video_pairs: {V} videos, the pass keeps at most {VIDEO_PAIRS_MAX_VIDEOS} "
+                         f"(ammc_video_pairs_max_videos) totals in a workgroup's LDS")
+    sorted_host = neg_host if Q <= P else pos_host         # the class the kernel sorts, video by video
+    seg = min(P, Q) if sorted_host is None else int(np.diff(sorted_host).max())
+    if seg > VIDEO_PAIRS_MAX_SEGMENT and sorted_host is not None:
+        raise ValueError(f"video_pairs: a video has {seg} frames of the smaller class, the pass sorts at most "
+                         f"{VIDEO_PAIRS_MAX_SEGMENT} (ammc_video_pairs_max_segment) in a workgroup's LDS")
+    _need_cuda(chan)
+    if seg > VIDEO_PAIRS_MAX_SEGMENT:                         # device offsets and a large class: its longest segment is needed
+        seg = int((neg_off if Q <= P else pos_off).diff().max())
+        if seg > VIDEO_PAIRS_MAX_SEGMENT:
+            raise ValueError(f"video_pairs: a video has {seg} frames of the smaller class, the pass sorts at most "
+                             f"{VIDEO_PAIRS_MAX_SEGMENT} (ammc_video_pairs_max_segment) in a workgroup's LDS")
+    if pos_host is not None:
+        pos_off = torch.from_numpy(pos_host.astype(np.int32)).to(dev)
+    if neg_host is not None:
+        neg_off = torch.from_numpy(neg_host.astype(np.int32)).to(dev)
+    if out is None:
+        out = torch.empty((G, S, V, V), device=dev, dtype=torch.int64)
+    elif tuple(out.shape) != (G, S, V, V) or out.dtype != torch.int64 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"video_pairs: out must be contiguous torch.int64 {(G, S, V, V)} on {dev}")
+    lib = _lib.load()
+    _lib.check(lib.ammc_video_pairs_f32(_ptr(chan), rs, K, N, _ptr(weights), G, _ptr(smooth), S, _ptr(pos_idx), P, _ptr(neg_idx),
+                                        Q, _ptr(pos_off), _ptr(neg_off), V, max(seg, 1), _ptr(out), _stream(chan)), "video_pairs")
+    return out
+
+
+def bootstrap_pairs(pairs: torch.Tensor, mult: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[r, j] = sum over a, b of mult[r, a] * mult[r, b] * pairs[j, a, b] in exact int64 (csrc/video_pairs.hip,
+    `ammc_bootstrap_pairs_i64`): what `video_pairs`' blocks give for replicas that draw video x mult[r, x] times.  `pairs`
+    int64 [M, V, V] and `mult` int32 [B, V], contiguous, on the GPU, entries >= 0.  The caller keeps the precondition
+    of include/ammc_hip.h: 2 P_r Q_r < 2^63 per replica.  Returns int64 [B, M] (`out`, when given, contiguous).  One
+    launch on torch's current stream."""
+    if not isinstance(pairs, torch.Tensor) or not isinstance(mult, torch.Tensor):
+        raise ValueError("bootstrap_pairs: pairs and mult must be tensors")
+    if pairs.dim() != 3 or pairs.shape[1] != pairs.shape[2] or pairs.dtype != torch.int64 or pairs.shape[0] < 1 or pairs.shape[1] < 1:
+        raise ValueError(f"bootstrap_pairs: pairs must be int64 [M, V, V], got {pairs.dtype} {tuple(pairs.shape)}")
+    M, V = pairs.shape[0], pairs.shape[1]
+    if mult.dim() != 2 or mult.shape[1] != V or mult.shape[0] < 1 or mult.dtype != torch.int32:
+        raise ValueError(f"bootstrap_pairs: mult must be int32 [B, {V}], got {mult.dtype} {tuple(mult.shape)}")
+    if V > VIDEO_PAIRS_MAX_VIDEOS:
+        raise ValueError(f"bootstrap_pairs: {V} videos, at most {VIDEO_PAIRS_MAX_VIDEOS} (ammc_video_pairs_max_videos)")
+    dev = pairs.device
+    if mult.device != dev or not pairs.is_contiguous() or not mult.is_contiguous():
+        raise ValueError(f"bootstrap_pairs: pairs and mult must be contiguous and both on {dev}")
+    B = mult.shape[0]
+    _need_cuda(pairs)
+    if out is None:
+        out = torch.empty((B, M), device=dev, dtype=torch.int64)
+    elif tuple(out.shape) != (B, M) or out.dtype != torch.int64 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"bootstrap_pairs: out must be contiguous torch.int64 {(B, M)} on {dev}")
+    _lib.check(_lib.load().ammc_bootstrap_pairs_i64(_ptr(pairs), M, V, _ptr(mult), B, _ptr(out), _stream(pairs)), "bootstrap_pairs")
+    return out
 
 
 # ---- pixel-level evaluation (csrc/pixel_scores.hip) -------------------------------------------

@@ -10,15 +10,21 @@ grid's lowest equal error rate, highest average precision and the precision-reca
 - "eer_at_lam_map" (on the full ROC curve, interpolated), "eer_vertex_at_lam_map" (at a vertex), "eer_reference_at_lam_map"
 (the reference's literal `compute_eer`), "pr_auc_at_lam_map" and "threshold_eer_at_lam_map"; `--positive anomalous` scores
 the anomalous class as the positive one.
+`--videos` (bare, without the number of synthetic videos that `--videos N` sets) adds the per-video pass (DESIGN.md section
+5.29): "macro_auc_best" (the grid's highest macro AUC, at "best_macro"), "macro_auc_at_lam_map", "videos", "videos_scored",
+the video-bootstrap percentile intervals "auc_ci_best" (of "best"), "auc_ci_at_lam_map", "macro_auc_ci_best", "best_share", "delta_best_vs_lam_map" {mean, ci}, "replicas",
+"replicas_dropped", "seed", "level" and "video_ms"; `--replicas B`, `--seed S` and `--level L` set the bootstrap.
 
     python -m ammcnet_aaai2021_amd.run_fusion --synthetic [--save_records REC.npz] [--out GRID.npz]
     python -m ammcnet_aaai2021_amd.run_fusion --records REC.npz --channels rgb_img_pred,rgb_ssim,rgb_fea_comm,op_fea_comm
     python -m ammcnet_aaai2021_amd.run_fusion --data FILE.pt --ckpt model.pth --step 0.05 --channels ...
+    python -m ammcnet_aaai2021_amd.run_fusion --records REC.npz --videos --replicas 1000 --seed 0 --level 0.95
 """
 from __future__ import annotations
 
 import argparse
 import json
+import sys
 
 import numpy as np
 
@@ -36,7 +42,8 @@ def build_parser():
     p.add_argument("--step", type=float, default=None,
                    help="weight step of the grid (default: the reference's 100 x 20 grid for two channels, 0.1 otherwise)")
     p.add_argument("--out", default=None, help="write auc, two_u, weights and smooth to this .npz")
-    p.epilog = "curve options (a parser of their own, so that the namespace above is what it was):\n" + curves_parser().format_help()
+    p.epilog = "curve options (a parser of their own, so that the namespace above is what it was):\n" + curves_parser().format_help() \
+        + "\nvideo options (likewise; a bare --videos, with no number behind it, is the switch):\n" + videos_parser().format_help()
     p.formatter_class = argparse.RawDescriptionHelpFormatter
     return p
 
@@ -49,10 +56,41 @@ def curves_parser():
     return p
 
 
-def parse_args(argv=None):
-    """(the entry's namespace, exactly what `build_parser` gave before the curve options existed; theirs)"""
+def videos_parser():
+    p = argparse.ArgumentParser(add_help=False, usage=argparse.SUPPRESS, allow_abbrev=False)
+    p.add_argument("--replicas", type=int, default=1000, help="bootstrap replicas of --videos (videos drawn with replacement)")
+    p.add_argument("--seed", type=int, default=0, help="seed of the replicas' multiplicity table")
+    p.add_argument("--level", type=float, default=0.95, help="level of the percentile intervals")
+    return p
+
+
+def _is_count(tok: str) -> bool:
+    try:
+        int(tok)
+    except ValueError:
+        return False
+    return True
+
+
+def split_videos_switch(argv):
+    """(argv without the bare `--videos` tokens, whether there was one).  `--videos N` has been the number of synthetic
+    videos since before the per-video pass and stays that; `--videos` with no integer behind it is the switch."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    bare = [i for i, tok in enumerate(argv) if tok == "--videos" and (i + 1 == len(argv) or not _is_count(argv[i + 1]))]
+    return [tok for i, tok in enumerate(argv) if i not in bare], bool(bare)
+
+
+def parse_args(argv=None, videos: bool = False):
+    """(the entry's namespace, exactly what `build_parser` gave before the curve options existed; theirs) - and with
+    `videos` a third: the video options', its `videos` the bare switch"""
+    argv, switch = split_videos_switch(argv)
     a, rest = build_parser().parse_known_args(argv)
-    return a, curves_parser().parse_args(rest)
+    if not videos:
+        return a, curves_parser().parse_args(rest)
+    cv, rest = curves_parser().parse_known_args(rest)
+    vd = videos_parser().parse_args(rest)
+    vd.videos = switch
+    return a, cv, vd
 
 
 def flatten_records(rec: dict, gt) -> dict:
@@ -86,7 +124,7 @@ def evaluate(a, dev):
 
 
 def main(argv=None):
-    a, cv = parse_args(argv)
+    a, cv, vd = parse_args(argv, videos=True)
     if a.maps_dir or a.ssim_maps:
         raise SystemExit("run_fusion writes no maps: --maps_dir / --ssim_maps belong to run_quality")
     channels = tuple(c.strip() for c in a.channels.split(",") if c.strip())
@@ -113,6 +151,19 @@ def main(argv=None):
             out.update({f"{k}_at_lam_map": cur["at_lam_map"][k] for k in ("eer", "eer_vertex", "eer_reference", "pr_auc", "ap",
                                                                           "threshold_eer")})
         arrays = {k: cur[k] for k in ("eer", "eer_vertex", "ap", "pr_auc", "threshold_eer", "pts")}
+    if vd.videos:
+        vid = harness.sweep_videos(rec, gt, channels, weights=weights, replicas=vd.replicas, seed=vd.seed, level=vd.level, device=dev)
+        out.update(macro_auc_best=vid["best_macro"]["macro_auc"], videos=vid["videos"], videos_scored=vid["videos_scored"],
+                   auc_ci_best=vid["best"]["auc_ci"], macro_auc_ci_best=vid["best_macro"]["macro_auc_ci"],
+                   best_share=vid["best_share"], replicas=vid["replicas"], replicas_dropped=vid["replicas_dropped"],
+                   seed=vid["seed"], level=vid["level"], video_ms=round(vid["video_ms"], 4),
+                   best_macro={k: v for k, v in vid["best_macro"].items() if k != "per_video_auc"})
+        arrays.update(macro_auc=vid["macro_auc"], auc_ci=vid["auc_ci"], macro_auc_ci=vid["macro_auc_ci"],
+                      per_video_auc=vid["best"]["per_video_auc"], pairs_best=vid["best"]["pairs"])
+        if "at_lam_map" in vid:
+            out.update(macro_auc_at_lam_map=vid["at_lam_map"]["macro_auc"], auc_ci_at_lam_map=vid["at_lam_map"]["auc_ci"],
+                       delta_best_vs_lam_map=vid["delta_best_vs_lam_map"])
+            arrays.update(per_video_auc_at_lam_map=vid["at_lam_map"]["per_video_auc"], pairs_at_lam_map=vid["at_lam_map"]["pairs"])
     if a.out:
         np.savez(a.out, auc=res["auc"], two_u=res["two_u"], weights=res["weights"],
                  smooth=harness.smoothing_pairs(res["lam_smooth"]), **arrays)

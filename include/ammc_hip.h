@@ -888,6 +888,54 @@ int ammc_curve_sweep_f32(const float* chan, int64_t chan_rs, int32_t k, int32_t 
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-video pair counts (csrc/video_pairs.hip): ammc_fusion_sweep_f32's count split by the video of either frame - what
+ * the macro AUC and a bootstrap over videos are made of.
+ * chan, chan_rs, k, n, w, g, sm, s, pos_idx, n_pos, neg_idx, n_neg and key[i] are exactly those of ammc_fusion_sweep_f32:
+ * rounded fp32, left to right, nothing contracted, key = t + 0.0f, the smoothing's neighbour taken across the WHOLE
+ * sequence - a video's first scored frame keeps the previous video's last frame as its neighbour.
+ *   pos_off  int32 [v + 1]: video x's positive frames are pos_idx[pos_off[x] .. pos_off[x + 1]); neg_off int32 [v + 1]
+ *            likewise into neg_idx.  Non-decreasing, the first entry 0, the last n_pos (n_neg); a video may have no frame
+ *            of either class, or of both.  DEVICE arrays, like the others.  (An offset outside its list is clamped into
+ *            it and a segment to max_segment: meaningless counts, never an access outside an array.)
+ *   max_segment  the caller's bound on the longest segment of the class that is sorted - the smaller one, the negatives
+ *            when n_neg <= n_pos: it sizes the workgroup's LDS.  The size of that class is always a valid bound.
+ *   pairs    int64 [g][s][v][v]:
+ *              pairs[gi][si][a][b] = sum over the positive frames p of video a and the negative frames q of video b of
+ *                                    (2 * [key_p > key_q] + [key_p == key_q])
+ *            exact.  Every element is written exactly once by a plain store, a pair with an empty side as 0: nothing
+ *            needs clearing beforehand.
+ * The sum of a block is two_u[gi][si]; pairs[a][a] / (2.0 * P_a * Q_a) is video a's own AUC; a replica that draws video
+ * x mult[x] times has two_u = sum_ab mult[a] * mult[b] * pairs[a][b] over 2 * (sum mult[a] P_a) * (sum mult[b] Q_b).
+ * One launch, one workgroup per (grid point, video of the sorted class): that video's keys are sorted in LDS, the other
+ * class is walked once, each frame located by two binary searches and its count added to its video's int64 total in LDS
+ * (a wave's sum, one integer LDS add).  No float arithmetic beyond the key, no global atomics, nothing passes between
+ * workgroups: the same integers on every launch, for a point alone or inside a grid, on every stream.
+ * Capacity: max_segment <= ammc_video_pairs_max_segment() = 32768, v <= ammc_video_pairs_max_videos() = 1024 (together
+ * 140 KiB of the CU's 160 KiB of LDS).
+ * AMMC_EINVAL: everything ammc_fusion_sweep_f32 refuses but its capacity; a null offset vector or one not 4-byte aligned;
+ * v < 1 or over its capacity; max_segment < 1 or over its capacity.  AMMC_EUNSUP: g * s * v >= 2^31 (the grid's x
+ * dimension).  All of them are decided before any HIP call.
+ *
+ * ammc_bootstrap_pairs_i64: the bilinear form above for b multiplicity rows and m blocks at once.
+ *   pairs    int64 [m][v][v], every entry >= 0 (ammc_video_pairs_f32's output, [g * s] flattened, or any part of it)
+ *   mult     int32 [b][v], every entry >= 0: how often replica r draws video x
+ *   out      int64 [b][m]:  out[r][j] = sum over a, b of mult[r][a] * mult[r][b] * pairs[j][a][b]
+ * exact in int64 under the PRECONDITION the caller checks per replica: 2 * P_r * Q_r < 2^63 with P_r = sum mult[r][a] P_a
+ * and Q_r = sum mult[r][b] Q_b, the replica's own denominator - it bounds the sum, whose terms are all non-negative.
+ * One launch, a workgroup per (128 replicas, block), a thread per replica; one writer per element, plain stores.
+ * AMMC_EINVAL: a null pointer; m < 1, b < 1, v < 1 or v over ammc_video_pairs_max_videos(); pairs or out not 8-byte
+ * aligned, mult not 4-byte aligned.  AMMC_EUNSUP: more than 65535 * 128 replicas (the grid's y dimension).
+ * ---------------------------------------------------------------------------------------- */
+int ammc_video_pairs_max_segment(void);
+int ammc_video_pairs_max_videos(void);
+int ammc_video_pairs_f32(const float* chan, int64_t chan_rs, int32_t k, int32_t n, const float* w, int32_t g, const float* sm,
+                         int32_t s, const int32_t* pos_idx, int32_t n_pos, const int32_t* neg_idx, int32_t n_neg,
+                         const int32_t* pos_off, const int32_t* neg_off, int32_t v, int32_t max_segment, int64_t* pairs,
+                         void* stream);
+int ammc_bootstrap_pairs_i64(const int64_t* pairs, int32_t m, int32_t v, const int32_t* mult, int32_t b, int64_t* out,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pixel-level evaluation (csrc/pixel_scores.hip): what the pixel-level criterion of Mahadevan et al. needs of a score
  * map and a ground-truth mask, per sample, from a pass of its own.
  *   map      fp32 [batch][h][w], higher = more anomalous; a sample contiguous (h * w floats), samples map_bs floats apart
